@@ -21,10 +21,17 @@ report fewer GPUs than asked for.  Every rank runs its own batch (weak scaling)
 and each step ends with the RCCL all-gather of the per-pair boxes - the only
 collective on the path; ``n_gpus`` in the output is the process group's size.
 
+A plain run does only what the headline figure needs: it sets up, warms up
+(W steps), times ONE region of exactly K steps (region 1 below), writes the
+last step's outputs if ``--dump-outputs DIR`` is given and prints the result
+line.  Everything else (regions 2-4, the calibration, power samples, the RCCL
+world-1 regions, the CPU baseline, end-to-end and other-config figures) runs
+only with ``--full``.
+
 Timed regions (each: barrier + synchronize, exactly K steps, barrier +
-synchronize, max over ranks) are repeated ``--repeats`` times and the MEDIAN
-region is reported (min / max alongside): a 20-step region lasts ~7 ms, too
-short to be stable alone.  Regions:
+synchronize, max over ranks) are repeated ``--repeats`` times (default 1; 9
+with ``--full``) and the MEDIAN region is reported (min / max alongside): a
+20-step region lasts ~7 ms, too short to be stable alone.  Regions:
   1. ``value`` / ``ms_per_step``: consecutive steps alternate over ``--streams``
      HIP streams (default 3) with 64-token encoder workgroups, so the next
      batch's kernels fill the CUs a batch of 8 pairs leaves idle.  Every step
@@ -38,8 +45,13 @@ short to be stable alone.  Regions:
   4. ``exact_f32``: the same workload on an OETR_DTYPE_F32 handle (true fp32 MFMA
      products), timed the same way, so the strict-fp32 figure is driver-timed too.
 
-Rank 0 prints ONE JSON line.  ``cpu_baseline`` is the oracle (torch CPU
-restatement of the reference) timed on this box's host cores (rank 0, N=1).
+Rank 0 prints ONE JSON line.  ``cpu_baseline`` (``--full``) is the oracle
+(torch CPU restatement of the reference) timed on this box's host cores (rank 0, N=1).
+
+``--dump-outputs DIR``: after the timed steps, what the timed path returned in
+its last step - the two [n,4] box tensors of ``boxes_from_features`` - as
+``DIR/box1.npy`` / ``DIR/box2.npy`` (float32; ``_rank<r>`` appended at N > 1).
+Inputs are seeded, so runs with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -91,8 +103,15 @@ def parse_args(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--repeats', type=int, default=9,
-                    help='timed regions of --steps steps each; the median region is reported')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each; the median region is reported (default 1, 9 with --full)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: serial regions, per-kernel traces and rooflines, '
+                         'calibration, power samples, the exact-fp32 leg, RCCL at world size 1, the CPU baseline, '
+                         'end-to-end and other-config figures (a plain run times the --steps steps of `value` only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path returned in its last step as '
+                         'DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
     ap.add_argument('--pairs-per-gpu', type=int, default=8)
     ap.add_argument('--size', type=int, default=640)
     ap.add_argument('--size2', type=int, default=None,
@@ -145,7 +164,39 @@ def parse_args(argv=None):
                          'pair list (640x640 vs 640x640 and 640x640 vs 1280x1280, --pairs-per-gpu of each per '
                          'GPU), buckets it by (L1, L2), runs its contiguous shard of every bucket and all-gathers '
                          'the boxes per bucket; reports the per-rank step-time spread')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as ``out_dir/<name>.npy``, float64 kept, everything else as
+    float32.  Above ``limit`` bytes in all, each array is cut to a fixed, seeded sample of its
+    flattened elements (in proportion to its size, indices ascending), so that two runs with the
+    same arguments still compare element for element.  Returns {name: (shape, sampled)}."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    budget = limit - 4096 * len(arrs)            # (room for the .npy headers)
+    info = {}
+    for name, a in arrs.items():
+        shape, sampled = list(a.shape), total > limit
+        if sampled:
+            keep = max(1, min(a.size, a.size * budget // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f'{name}.npy', a)
+        info[name] = (shape, sampled)
+    return info
 
 
 def free_port():
@@ -376,7 +427,7 @@ def bench_full_attention(args, device):
            'unit': 'TFLOP/s (algorithmic)', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
            'higher_is_better': True, 'data': 'synthetic', 'vs_baseline': None,
            'config': {'workload': f'{n} images, L=S={L}, 8 heads, D=32, fp32 in/out'}}
-    variants = {}
+    variants, last = {}, {}
     for name in pkg.FULL_ATTENTION_VARIANTS:
         fn = lambda: pkg.full_attention(q, k, v, variant=name)
         for _ in range(args.warmup):
@@ -387,10 +438,12 @@ def bench_full_attention(args, device):
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
             for _ in range(args.steps):
-                fn()
+                o = fn()
             ev1.record()
             torch.cuda.synchronize()
             regions.append(ev0.elapsed_time(ev1) / args.steps)
+        if args.dump_outputs:
+            last[name] = o.cpu().numpy()
         ms = statistics.median(regions)
         cost, pipe_peak, basis = MFMA_COST['f32' if name == 'f32' else 'f32_split_f16']
         ach = flop / (ms * 1e-3) / 1e12
@@ -403,6 +456,8 @@ def bench_full_attention(args, device):
     out['dtype'] = 'f32'
     out['roofline'] = dict(kernel=f'k_full_attention [{best}]', **variants[best])
     out['variants'] = variants
+    if args.dump_outputs:       # the output of the headline variant's last launch
+        dump_outputs(args.dump_outputs, {'attention_out': last[best]})
     print(json.dumps(out))
 
 
@@ -673,6 +728,7 @@ def bench_mixed(args, device, world, rank, use_pg, pkg):
             for wk in work:
                 with torch.cuda.stream(streams[j % len(streams)]):
                     b1, b2 = eng.forward(wk['f1'], wk['f2'], wk['p1'], wk['p2'], wk['hw'], wk['hw2'])
+                    wk['last'] = (b1, b2)
                     if gatherer is not None:
                         gatherer.submit(b1, b2, n_pairs=wk['n_bucket'])
                 j += 1
@@ -691,6 +747,10 @@ def bench_mixed(args, device, world, rank, use_pg, pkg):
     region(max(1, args.warmup))
     regs = sorted((region(args.steps) for _ in range(max(1, args.repeats))), key=lambda r: r[0])
     dt, per_rank = regs[len(regs) // 2]
+    if args.dump_outputs:       # every bucket's boxes of the last step (this rank's shard)
+        sfx = f'_rank{rank}' if world > 1 else ''
+        dump_outputs(args.dump_outputs, {f'box{s + 1}_bucket{i}{sfx}': wk['last'][s].cpu().numpy()
+                                         for i, wk in enumerate(work) for s in (0, 1)})
     if rank != 0:
         return None
     pairs_step = sum(wk['n_bucket'] for wk in work)
@@ -853,6 +913,7 @@ def main():
         return eng, (args.enc_tile or (64 if (overlapped and half and eng.attention == 'linear') else 0))
 
     step_spread = {}
+    last_boxes = {}
 
     def run_mode(m, ns):
         """One timed region: exactly --steps steps over `ns` streams."""
@@ -860,6 +921,7 @@ def main():
             # consecutive steps alternate over the model's streams (one workspace per stream in
             # the engine); every step is a full batch of n pairs through the whole path
             b1, b2 = m.boxes_from_features(feat1, feat2, pos, pos2, hw, hw2)
+            last_boxes['boxes'] = (b1, b2)      # (final once the region's hip_flush has settled them)
             gatherer = pg['gatherer']
             if gatherer is not None:
                 # the all-gather of a batch's boxes is ISSUED once the model has settled that batch's deferred
@@ -901,16 +963,24 @@ def main():
             dt = run_mode(m, 1)
         return trace.summary(), dt
 
-    def measure(precision, with_serial_trace):
+    def measure(precision, with_serial_trace, plain=False):
+        """plain: only what `value` needs - warm-up and the timed region(s) of the overlapped mode."""
         m = model_for(precision)
-        eng, _ = configure(m, 1, False)
-        res = {'engine': eng, 'model': m}
-        warm(m, 1)
+        res = {'model': m}
+        if not plain:
+            configure(m, 1, False)
+            warm(m, 1)
         eng, tile_overlap = configure(m, n_streams, n_streams > 1)
+        res['engine'] = eng
         res['tile_overlap'] = tile_overlap
         warm(m, n_streams)
         res['overlap'] = repeated(m, n_streams)              # -> value (no instrumentation)
         res['rank_spread'] = step_spread.get('last')
+        if args.dump_outputs and precision == args.precision:    # the last timed step's boxes, outside the timing
+            res['outputs'] = {'box1': last_boxes['boxes'][0].cpu().numpy(),
+                              'box2': last_boxes['boxes'][1].cpu().numpy()}
+        if plain:
+            return res
         if not args.no_trace:
             # same K steps on ONE stream (kernel durations only mean something when launches
             # do not share the chip), in the tile shape that produced `value`, with the
@@ -923,7 +993,7 @@ def main():
             res['trace_serial_shape'] = traced(m, eng)
         return res
 
-    if world == 1 and not use_pg and not args.no_trace:
+    if args.full and world == 1 and not use_pg and not args.no_trace:
         # the two yardsticks that belong to THIS box and THIS run: what an empty HIP-event bracket reads, and the
         # dense f16 MFMA rate the chip sustains at its power cap (with the clock it held, from rocm-smi beside it)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
@@ -942,10 +1012,13 @@ def main():
                 CALIB['f16_sustained'] = statistics.median(rates) if rates else None
             except Exception as e:
                 print(f'[bench] MFMA-rate calibration failed: {e!r}', file=sys.stderr)
-    main_res = measure(args.precision, with_serial_trace=True)
+    main_res = measure(args.precision, with_serial_trace=True, plain=not args.full)
     eng = main_res['engine']
+    if args.dump_outputs:
+        sfx = f'_rank{rank}' if world > 1 else ''
+        dump_outputs(args.dump_outputs, {k + sfx: v for k, v in main_res['outputs'].items()})
     power = None
-    if world == 1 and not use_pg and not args.no_power:
+    if args.full and world == 1 and not use_pg and not args.no_power:
         # what the chip draws and clocks while each mode runs (not timed; rank 0 at N = 1 only)
         m = main_res['model']
 
@@ -961,7 +1034,7 @@ def main():
         configure(m, 1, False)
         power['serial'] = power_sample(keep_running(1, False))
     exact_res = None
-    if args.precision == 'f32_split_f16' and not args.no_exact_f32 and args.attention == 'linear':
+    if args.full and args.precision == 'f32_split_f16' and not args.no_exact_f32 and args.attention == 'linear':
         exact_res = measure('f32', with_serial_trace=False)
     # RCCL on the N = 1 line: the same two regions with a process group of ONE rank up -
     # librccl loaded and bound to the device, the box all-gather of every batch issued by BoxGatherer, the
@@ -969,7 +1042,8 @@ def main():
     # 5 x --steps per region (the barrier collective's own host latency, 0.2-0.45 ms, is a fixed cost per
     # region: profiles/r5_pg_streams.txt).  RCCL's banner goes through C stdio: stdout is parked on stderr.
     rccl_w1 = None
-    if world == 1 and not use_pg and standard and args.precision == 'f32_split_f16' and not args.no_rccl_world1:
+    if (args.full and world == 1 and not use_pg and standard and args.precision == 'f32_split_f16'
+            and not args.no_rccl_world1):
         saved_fd, saved_steps = os.dup(1), args.steps
         try:
             sys.stdout.flush()
@@ -1051,7 +1125,8 @@ def main():
         'scaling': 'weak', 'vs_baseline': None, 'dtype': dtype,
         'gemm_mode': GEMM_MODE_TEXT[args.precision],
         'data': 'synthetic',
-        'timing': {'repeats': args.repeats, 'statistic': 'median region of --steps steps',
+        'timing': {'repeats': args.repeats,
+                   'statistic': 'median region of --steps steps' if args.repeats > 1 else 'one region of --steps steps',
                    'ms_per_step_min': round(e_min / args.steps * 1e3, 4),
                    'ms_per_step_max': round(e_max / args.steps * 1e3, 4)},
         'config': {'workload': tag + f'batch={n} pairs/GPU, {args.size}x{args.size}'
@@ -1080,13 +1155,14 @@ def main():
         # the roof that binds: the hot path runs the socket at its power cap in both modes, and the shader clock is
         # what the cap leaves (MFMA peaks in `roofline` are quoted at the nominal 2.4 GHz)
         out['power'] = power
-    s_med, s_min, s_max = main_res['serial']
-    # the same K steps strictly one after the other on one stream (batch latency;
-    # encoder tile = library default)
-    out['serial'] = {'ms_per_step': round(s_med / args.steps * 1e3, 4),
-                     'pairs_per_s': round(n_total * args.steps / s_med, 1),
-                     'ms_per_step_min': round(s_min / args.steps * 1e3, 4),
-                     'ms_per_step_max': round(s_max / args.steps * 1e3, 4)}
+    if 'serial' in main_res:        # (--full)
+        s_med, s_min, s_max = main_res['serial']
+        # the same K steps strictly one after the other on one stream (batch latency;
+        # encoder tile = library default)
+        out['serial'] = {'ms_per_step': round(s_med / args.steps * 1e3, 4),
+                         'pairs_per_s': round(n_total * args.steps / s_med, 1),
+                         'ms_per_step_min': round(s_min / args.steps * 1e3, 4),
+                         'ms_per_step_max': round(s_max / args.steps * 1e3, 4)}
     if 'trace_overlap_shape' in main_res:
         kern, t_s = main_res['trace_overlap_shape']
         rb = roofline_block(kern, args.precision, tokens, tile_overlap or 32, args.steps, t_s, standard, extra_flop,
@@ -1146,7 +1222,7 @@ def main():
                  rccl_w1['librccl_mapped']] if 'error' not in rccl_w1 else rccl_w1)
     if rccl_w1 is not None:
         out['rccl_world1'] = rccl_w1
-    if not args.no_cpu_baseline and world == 1:   # host-core baseline: rank 0 at N=1 only
+    if args.full and not args.no_cpu_baseline and world == 1:   # host-core baseline: rank 0 at N=1 only
         base, ref_boxes = cpu_baseline(weights, feat1, feat2, args.size, size2)
         out['cpu_baseline'] = base
         from oracle import oetr_oracle as orc
@@ -1155,9 +1231,9 @@ def main():
                          orc.bbox_iou_aligned(mine[1].cpu(), ref_boxes[1])])
         out['iou_vs_cpu_min'] = round(float(iou.min()), 6)
         out['speedup_vs_cpu'] = round(value / base['value'], 1)
-    if eng.precision in eng.F16_RANGE:
+    if args.full and eng.precision in eng.F16_RANGE:
         out['f16_range_flag'] = eng.query_flags()
-    if not args.no_e2e and world == 1:
+    if args.full and not args.no_e2e and world == 1:
         try:     # whole forward_dummy incl. the PyTorch/MIOpen backbone (host code)
             out.update(end_to_end(args, model, device, n, size2, pkg))
             out['end_to_end']['hot_ms_serial'] = out['serial']['ms_per_step']
@@ -1165,7 +1241,7 @@ def main():
                 out['cpu_baseline_full_forward'] = cpu_full_forward(model, args.size)
         except Exception as e:  # host-side extras must never break the bench line
             out['end_to_end_error'] = repr(e)[:200]
-    if (not args.no_other_configs and world == 1 and standard and args.precision == 'f32_split_f16'
+    if (args.full and not args.no_other_configs and world == 1 and standard and args.precision == 'f32_split_f16'
             and not args.no_trace):
         try:     # configs[2] / [3] / [4] under the same clock (short regions, ~20 s)
             oc = other_configs(args, device, pkg)

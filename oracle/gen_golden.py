@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Generate tests/golden/*.npz by running the REFERENCE implementation.
 
-Runs only in the build container (needs /root/reference, read-only).  The
-reference's Python never leaves this container: what is committed are inputs
-recipes (seeds), expected outputs and this script.
+Runs against the snapshot of the reference's Python modules that ``build()`` places
+in ``oracle/_ref/`` (``oracle/ref_snapshot.py``; kept out of git).  The reference's
+Python is never committed: what is committed are input recipes (seeds), expected
+outputs and this script.
 
 The reference imports five packages this image lacks.  They are
 stubbed in ``sys.modules`` *for this process only*:
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 REPO = Path(__file__).resolve().parents[1]
-REF = Path('/root/reference')
+REF = REPO / 'oracle' / '_ref'          # oracle/ref_snapshot.py
 sys.dont_write_bytecode = True
 sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REF))
@@ -370,7 +371,7 @@ CROP_CASES = [
 def gen_crop(out_dir):
     """Box -> crop step from the reference's own code: the overlap
     branch of ``Matching.forward`` (evaluation.py:66-170; its function body is compiled
-    straight from /root/reference/evaluation.py - importing that module would drag in
+    straight from the reference's evaluation.py - importing that module would drag in
     h5py, the extractors and the matchers) with ``tensor_overlap_crop`` /
     ``patch_resize`` imported from dloc/core/utils/utils.py.  cv2 is not installed:
     ``cv2.resize`` is the oracle's restatement of OpenCV's bicubic, so the PIXELS of the
@@ -555,6 +556,8 @@ def main():
     ap.add_argument('--out', default=str(REPO / 'tests' / 'golden'))
     ap.add_argument('--only', default=None, help='generate one family only (e.g. crop)')
     args = ap.parse_args()
+    if not (REF / 'src' / 'model.py').is_file():
+        sys.exit(f'no reference snapshot in {REF}: build() (oracle/ref_snapshot.py) makes it from a reference checkout')
     out_dir = Path(args.out)
     out_dir.mkdir(parents=True, exist_ok=True)
     torch.set_grad_enabled(False)

@@ -41,3 +41,40 @@ def test_roofline_block_carries_both_yardsticks():
     finally:
         bench.CALIB.clear()
         bench.CALIB.update(saved)
+
+
+def test_plain_run_times_steps_once_and_full_keeps_the_repeats():
+    """A plain run times exactly --steps steps (one region); --full keeps the nine-region median."""
+    import bench
+    plain = bench.parse_args(['--steps', '7', '--warmup', '2'])
+    assert (plain.full, plain.repeats, plain.steps, plain.dump_outputs) == (False, 1, 7, None)
+    full = bench.parse_args(['--full'])
+    assert full.full and full.repeats == 9
+    assert bench.parse_args(['--full', '--repeats', '3']).repeats == 3
+    assert bench.parse_args(['--dump-outputs', 'out']).dump_outputs == 'out'
+
+
+def test_dump_outputs_dtypes_and_size_cap(tmp_path):
+    """float64 stays float64, everything else is written as float32; above the cap every array is cut
+    to the same seeded sample on every call, within the cap in all."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    small = {'box1': rng.random((8, 4), dtype=np.float32), 'box2': rng.random((8, 4)).astype(np.float16),
+             'wide': rng.random(5)}
+    info = bench.dump_outputs(tmp_path / 'a', small)
+    assert info == {'box1': ([8, 4], False), 'box2': ([8, 4], False), 'wide': ([5], False)}
+    assert np.load(tmp_path / 'a' / 'box1.npy').tobytes() == small['box1'].tobytes()
+    assert np.load(tmp_path / 'a' / 'box2.npy').dtype == np.float32
+    assert np.load(tmp_path / 'a' / 'wide.npy').dtype == np.float64
+    big = {'a': rng.random(30000, dtype=np.float32), 'b': rng.random((100, 50))}
+    limit = 64 * 1024
+    for d in ('b1', 'b2'):
+        info = bench.dump_outputs(tmp_path / d, big, limit=limit)
+        assert info == {'a': ([30000], True), 'b': ([100, 50], True)}
+    files = [tmp_path / d / f'{k}.npy' for d in ('b1', 'b2') for k in big]
+    assert sum(f.stat().st_size for f in files[:2]) <= limit
+    for k in big:
+        x, y = np.load(tmp_path / 'b1' / f'{k}.npy'), np.load(tmp_path / 'b2' / f'{k}.npy')
+        assert x.size > 0 and x.tobytes() == y.tobytes()
+        assert np.isin(x, big[k].reshape(-1)).all()

@@ -1,7 +1,10 @@
-"""The committed fixtures ARE what the reference produces: when the reference tree is
-present (the build container; it does not exist on the GPU box) the DEFAULT generator
-command ``python oracle/gen_golden.py --out <tmp>`` is re-run - importing the real
-reference - and every family is compared bit for bit with ``tests/golden/``.
+"""The committed fixtures ARE what the reference produces: when ``build()`` has placed the
+snapshot of the reference's Python modules in ``oracle/_ref/`` (``oracle/ref_snapshot.py``; made
+only where a reference checkout is readable) the DEFAULT generator command
+``python oracle/gen_golden.py --out <tmp>`` is re-run - importing the real reference from that
+snapshot - and every family is compared bit for bit with ``tests/golden/``.  Bit-for-bit holds
+on the kind of CPU that produced the fixtures: the test runs where the snapshot was made
+(``ref_snapshot.made_here``: same CPU model and torch CPU dispatch level).
 
 Pins the generator as well as the fixtures: round 2's default command overwrote
 ``train_forward.npz`` with different data (the neck family had loaded seeded neck weights
@@ -16,10 +19,13 @@ import pytest
 
 REPO = Path(__file__).resolve().parents[1]
 GOLDEN = REPO / 'tests' / 'golden'
-REFERENCE = Path('/root/reference')
+if str(REPO) not in sys.path:
+    sys.path.insert(0, str(REPO))
+from oracle import ref_snapshot  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not (REFERENCE / 'src' / 'model.py').exists(),
-                                reason='needs the reference tree (build container only)')
+pytestmark = pytest.mark.skipif(not ref_snapshot.made_here(),
+                                reason='needs the reference snapshot that build() places in oracle/_ref/, '
+                                       'made on a CPU like this one')
 
 
 @pytest.fixture(scope='module')

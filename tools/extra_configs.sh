@@ -5,7 +5,7 @@ TAG=${1:-r1}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/${TAG}_extra_configs.jsonl
 mkdir -p $ROOT/gpurun_out; : > $OUT
-run() { timeout 300 python $ROOT/bench.py --no-cpu-baseline --no-e2e "$@" >> $OUT 2>/dev/null; }
+run() { timeout 300 python $ROOT/bench.py --full --no-cpu-baseline --no-e2e "$@" >> $OUT 2>/dev/null; }
 run --pairs-per-gpu 1 --steps 200                                  # configs[0] shape: 1 pair @640
 run --pairs-per-gpu 64 --steps 40 --warmup 5                       # config 3: 64 pairs @640
 run --pairs-per-gpu 32 --size 1024 --steps 20 --warmup 3           # config 4: 32 pairs @1024 (32x32 tokens)

@@ -9,20 +9,20 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd $ROOT
 # ---- bench lines (driver-style invocations) --------------------------------
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 # the per-GEMM-site precision policy (the reduced mode inside the IoU bar): configs[2] / configs[4] shares
-timeout 300 python bench.py --steps 20 --warmup 5 --precision f32_split_qk16 --no-e2e > $OUT/bench_qk16.json 2>> $OUT/bench.err
-timeout 300 python bench.py --steps 20 --warmup 5 --precision f32_split_qk16 --size2 1280 --no-e2e > $OUT/bench_qk16_mixed.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --precision f32_split_qk16 --no-e2e > $OUT/bench_qk16.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --precision f32_split_qk16 --size2 1280 --no-e2e > $OUT/bench_qk16_mixed.json 2>> $OUT/bench.err
 # the all-rounded single-pass modes (miss the bar: comparison only)
-timeout 300 python bench.py --steps 20 --warmup 5 --precision bf16 --no-e2e --no-cpu-baseline > $OUT/bench_bf16.json 2>> $OUT/bench.err
-timeout 300 python bench.py --steps 20 --warmup 5 --precision f16 --size2 1280 --no-e2e --no-cpu-baseline > $OUT/bench_f16_mixed.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --precision bf16 --no-e2e --no-cpu-baseline > $OUT/bench_bf16.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --precision f16 --size2 1280 --no-e2e --no-cpu-baseline > $OUT/bench_f16_mixed.json 2>> $OUT/bench.err
 # RCCL executed at world size 1 (process group forced)
-OETR_BENCH_FORCE_PG=1 timeout 300 python bench.py --steps 20 --warmup 5 --no-e2e --no-cpu-baseline --no-exact-f32 2>> $OUT/bench.err | grep '^{' > $OUT/bench_rccl_world1.json
-timeout 300 python bench.py --steps 20 --warmup 5 --attention full --no-e2e --no-cpu-baseline > $OUT/bench_attention_full.json 2>> $OUT/bench.err
-OETR_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-e2e --no-exact-f32 2>> $OUT/bench.err | grep '^{' > $OUT/bench_gloo2.json
+OETR_BENCH_FORCE_PG=1 timeout 300 python bench.py --full --steps 20 --warmup 5 --no-e2e --no-cpu-baseline --no-exact-f32 2>> $OUT/bench.err | grep '^{' > $OUT/bench_rccl_world1.json
+timeout 300 python bench.py --full --steps 20 --warmup 5 --attention full --no-e2e --no-cpu-baseline > $OUT/bench_attention_full.json 2>> $OUT/bench.err
+OETR_BENCH_BACKEND=gloo timeout 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-e2e --no-exact-f32 2>> $OUT/bench.err | grep '^{' > $OUT/bench_gloo2.json
 # configs[4] as a mixed-scale job: bucket by (L1, L2), shard every bucket, per-rank step-time spread (2 ranks on this 1-GPU box, gloo)
-OETR_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --workload mixed --steps 10 --warmup 3 --precision f32_split_qk16 2>> $OUT/bench.err | grep '^{' > $OUT/bench_gloo2_mixed.json
-OETR_BENCH_FORCE_PG=1 timeout 300 python bench.py --workload mixed --steps 10 --warmup 3 --precision f32_split_qk16 2>> $OUT/bench.err | grep '^{' > $OUT/bench_rccl_world1_mixed.json
+OETR_BENCH_BACKEND=gloo timeout 300 python bench.py --full --gpus 2 --workload mixed --steps 10 --warmup 3 --precision f32_split_qk16 2>> $OUT/bench.err | grep '^{' > $OUT/bench_gloo2_mixed.json
+OETR_BENCH_FORCE_PG=1 timeout 300 python bench.py --full --workload mixed --steps 10 --warmup 3 --precision f32_split_qk16 2>> $OUT/bench.err | grep '^{' > $OUT/bench_rccl_world1_mixed.json
 timeout 600 python tools/trunk_autocast.py > $OUT/trunk_autocast.txt 2>> $OUT/bench.err
 # decoder chain on one / four workgroups per image: per-kernel events, serial steps, differences, concurrent streams
 timeout 600 python tools/decoder_split_ab.py > $OUT/decoder_split_ab.txt 2>> $OUT/bench.err
@@ -33,7 +33,7 @@ bash tools/extra_configs.sh $TAG > $OUT/extra_configs.log 2>&1
 mv $ROOT/gpurun_out/${TAG}_extra_configs.jsonl $OUT/extra_configs.jsonl 2>/dev/null
 # ---- rocprofv3: one process runs BOTH encoder shapes (3-stream pass with 64-token
 #      workgroups, then the serial pass with 32-token ones) --------------------------
-BENCH="python $ROOT/bench.py --no-cpu-baseline --no-e2e --no-trace --no-exact-f32 --no-rccl-world1 --no-power --steps 50 --warmup 5 --repeats 1"
+BENCH="python $ROOT/bench.py --full --no-cpu-baseline --no-e2e --no-trace --no-exact-f32 --no-rccl-world1 --no-power --steps 50 --warmup 5 --repeats 1"
 SERIAL32="$BENCH --streams 1"
 SERIAL64="$BENCH --streams 1 --enc-tile 64"
 cd /tmp
