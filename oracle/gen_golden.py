@@ -173,6 +173,12 @@ MASK_CASES = [
     ('s7_20x20_sharp', 7, True, 17, 3, (20, 20), (20, 20), (640, 640), (640, 640), 70, 'pad'),
     ('s8_15x20_25x10_sharp', 8, True, 18, 3, (15, 20), (25, 10), (480, 640), (800, 320), 71, 'holes'),
     ('s9_20x20_40x40', 9, False, 19, 2, (20, 20), (40, 40), (640, 640), (1280, 1280), 72, 'pad'),
+    # fractional and adversarial masks (oracle.make_mask_pattern), 63 / 65 tokens: image 0 weighted (the
+    # state carries m^2, the key sum m), image 1 the second 32-row tile cleared (side 1: the whole ragged
+    # last tile), image 2 only the last token valid; stored as float32, every second token row of the
+    # stage tensors (stride 2 keeps the last token of both grids and the file under 1 MB)
+    ('s10_7x9_5x13_sharp', 10, True, 20, 3, (7, 9), (5, 13), (224, 288), (160, 416), 73, 'weighted|tile32:1|last',
+     30),
 ]
 
 
@@ -188,6 +194,7 @@ def gen_hot(out_dir, model, cases=None, prefix='hot_', full_attention=False):
     for case in (cases or HOT_CASES):
         (tag, wseed, sharp, fseed, n, g1, g2, im1, im2) = case[:9]
         mask1 = mask2 = None
+        rows = case[11] if len(case) > 11 else 48     # sub()'s max_rows
         if len(case) > 9:   # MASK_CASES
             mask1 = orc.make_masks(case[9], n, *g1, kind=case[10])
             mask2 = orc.make_masks(case[9] + 100, n, *g2, kind=case[10])
@@ -239,13 +246,14 @@ def gen_hot(out_dir, model, cases=None, prefix='hot_', full_attention=False):
                     tlbr2=t2.numpy(), box1=b1.numpy(), box2=b2.numpy(),
                     memory1_fp=fp(m1), memory2_fp=fp(m2))
         if mask1 is not None:
+            mdt = np.uint8 if case[10] in ('pad', 'holes') else np.float32     # (0/1 kinds: uint8, as ever)
             data.update(mask_seed=np.int64(case[9]), mask_kind=np.str_(case[10]),
-                        mask1=mask1.numpy().astype(np.uint8), mask2=mask2.numpy().astype(np.uint8))
-        data['memory1'], data['memory1_step'] = sub(m1)
-        data['memory2'], data['memory2_step'] = sub(m2)
+                        mask1=mask1.numpy().astype(mdt), mask2=mask2.numpy().astype(mdt))
+        data['memory1'], data['memory1_step'] = sub(m1, rows)
+        data['memory2'], data['memory2_step'] = sub(m2, rows)
         for li in (0, 1):
             for side in (0, 1):
-                arr, st = sub(enc_out[li][side])
+                arr, st = sub(enc_out[li][side], rows)
                 data[f'enc{li}_x{side + 1}'] = arr
                 data[f'enc{li}_x{side + 1}_step'] = np.int64(st)
                 data[f'enc{li}_x{side + 1}_fp'] = fp(enc_out[li][side])

@@ -124,7 +124,10 @@ def make_masks(seed, n, hf, wf, kind='pad'):
     (``resize_mask``, src/model.py:256-258): kind 'pad' = image i's valid region is
     its top-left hv x wv corner (hv, wv drawn per image, at least half of the grid,
     image 0 fully valid); 'holes' = 'pad' with ~10 % of the valid tokens cleared as
-    well (masks need not be rectangles: the reference only multiplies by them)."""
+    well (masks need not be rectangles: the reference only multiplies by them).  Every
+    other kind is a pattern of ``make_mask_pattern``."""
+    if kind not in ('pad', 'holes'):
+        return make_mask_pattern(seed, n, hf, wf, kind)
     g = torch.Generator().manual_seed(int(seed))
     m = torch.zeros(n, hf, wf)
     for i in range(n):
@@ -134,6 +137,51 @@ def make_masks(seed, n, hf, wf, kind='pad'):
     if kind == 'holes':
         m = m * (torch.rand(n, hf, wf, generator=g) >= 0.1).float()
     return m
+
+
+def make_mask_pattern(seed, n, hf, wf, kind):
+    """Masks [n,hf,wf] (float32) laid out over the flattened token order the encoder kernels
+    tile (row l = y * wf + x).  ``kind`` is one pattern for every image, or patterns joined by
+    '|' for images 0, 1, ... (the last one repeats for the rest):
+      'full' / 'zero'  every token valid / none;
+      'weighted'       weights in (0, 1], ~20 % exact zeros, a few 1.5 and a few 1e-6 (non-zero:
+                       not filled, but almost no weight) - the reference multiplies phi(K) AND V
+                       by the mask, so the state carries m^2 and the key sum m;
+      'tileT:k'        every token valid but rows [k*T, (k+1)*T) (T = 32 or 64: one encoder tile);
+      'first' / 'last' only the first / the last token valid (the last sits in the ragged tile);
+      'one'            a single valid token at a seeded position;
+      'empty'          alone: image 0 fully valid, every other image empty ('zero').
+    Only uniform draws (``torch.rand``) from one seeded CPU generator, image by image."""
+    g = torch.Generator().manual_seed(int(seed))
+    kinds = ['full', 'zero'] if kind == 'empty' else kind.split('|')
+    L = hf * wf
+    m = torch.zeros(n, L)
+    for i in range(n):
+        k = kinds[min(i, len(kinds) - 1)]
+        if k == 'full':
+            m[i] = 1.0
+        elif k == 'zero':
+            pass
+        elif k == 'weighted':
+            m[i] = 1.0 - torch.rand(L, generator=g)                 # (0, 1]
+            order = torch.argsort(torch.rand(L, generator=g))
+            nz, nx = round(0.2 * L), max(1, L // 20)
+            m[i, order[:nz]] = 0.0
+            m[i, order[nz:nz + nx]] = 1.5
+            m[i, order[nz + nx:nz + 2 * nx]] = 1e-6
+        elif k.startswith('tile32:') or k.startswith('tile64:'):
+            t, j = int(k[4:6]), int(k[7:])
+            m[i] = 1.0
+            m[i, j * t:(j + 1) * t] = 0.0
+        elif k == 'first':
+            m[i, 0] = 1.0
+        elif k == 'last':
+            m[i, L - 1] = 1.0
+        elif k == 'one':
+            m[i, min(int(torch.rand(1, generator=g) * L), L - 1)] = 1.0
+        else:
+            raise ValueError(f'unknown mask kind {k!r}')
+    return m.view(n, hf, wf)
 
 
 def checksum(t):
