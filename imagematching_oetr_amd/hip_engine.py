@@ -317,37 +317,71 @@ def _query_flags(lib, fn, handle, ws, device, clear):
     return int(flags.value)
 
 
-class FlagTicket:
-    """A status word on its way to the host, nothing has synchronised.  Two kinds:
+def _gpu_device(device, who):
+    """``device`` (None: torch's current one) as a ``cuda`` device with an index."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != 'cuda':
+        raise OetrError(f'{who} needs a GPU device')
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    return device
 
-    * published (``oetr_forward*_flagslot``, ABI 6): the forward call's last kernel stores the word,
-      with ``FLAG_PUBLISHED`` set, into a mapped pinned host word that was zeroed before the call.
-      No dispatch and NO EVENT behind the batch (an event record is a marker packet on the stream:
-      measured 6 us of idle chip in front of the next batch's first kernel): ``value()`` polls the
-      word - by the time the next batch is submitted it has long arrived - and falls back to
-      synchronising the stream the call was enqueued on if it has not after ``POLL_S``.
-    * copied (``oetr_read_flags_async``): a 4-byte copy was ENQUEUED behind the calls it reports
-      on; ``value()`` waits for an event recorded right behind that copy."""
+
+def _stream_workspace(table, key, device, need):
+    """The workspace of HIP stream ``key`` in ``table`` (stream -> uint8 tensor on ``device``), grown to at
+    least ``need`` bytes: one workspace per stream - a handle is immutable, so calls on different streams
+    may overlap as long as their workspaces differ.  A new workspace's status block is zeroed
+    (``oetr_workspace_init``); a regrown one carries the old block over (a sticky flag survives)."""
+    old = table.get(key)
+    if old is not None and old.numel() >= need:
+        return old
+    ws = table[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    if old is None:
+        ws[:WORKSPACE_STATUS_BYTES].zero_()
+    else:
+        ws[:WORKSPACE_STATUS_BYTES].copy_(old[:WORKSPACE_STATUS_BYTES])
+    return ws
+
+
+def _destructor(destroy, attr='_h'):
+    """``__del__`` of a class whose objects own a library handle in ``attr``: ``lib.<destroy>`` it once,
+    quietly.  It reads no module global: it may run while the interpreter shuts down."""
+    def __del__(self):
+        h = getattr(self, attr, None)
+        setattr(self, attr, None)
+        if h:
+            try:
+                getattr(self.lib, destroy)(h)
+            except Exception:
+                pass
+    return __del__
+
+
+class FlagTicket:
+    """The status word of one ``oetr_forward*_flagslot`` call (ABI 6) on its way to the host: the call's
+    last kernel stores the word, with ``FLAG_PUBLISHED`` set, into a mapped pinned host word that was
+    zeroed before the call.  No dispatch and NO EVENT behind the batch (an event record is a marker packet
+    on the stream: measured 6 us of idle chip in front of the next batch's first kernel).
+
+    * eager call: ``value()`` polls the word - by the time the next batch is submitted it has long
+      arrived -, falls back to synchronising the stream the call was enqueued on after ``POLL_S``, and
+      keeps the value it read (the engine hands the word out again only once its ticket has it);
+    * call captured into a HIP graph: every replay rewrites the word, so ``value()`` reads it again
+      each time (valid once a replay has been synchronised; 0 before the first)."""
 
     POLL_S = 0.05
 
-    def __init__(self, slot, event, owner=None, index=None, stream=None, published=False):
-        self._slot, self._event = slot, event
+    def __init__(self, slot, stream=None, owner=None, index=None):
+        self._slot, self._stream, self._value = slot, stream, None
         self._owner, self._index = owner, index     # graph words: handed back by release()
-        self._stream, self._published = stream, published
-
-    def ready(self):
-        if self._published and self._stream is not None:
-            return bool(int(self._slot.item()) & FLAG_PUBLISHED)
-        return self._event is None or self._event.query()
 
     def value(self):
-        if self._event is not None:
-            self._event.synchronize()
-        if not self._published:
-            return int(self._slot.item())
+        if self._value is not None:
+            return self._value
         word = int(self._slot.item()) & 0xffffffff
-        if not word & FLAG_PUBLISHED and self._stream is not None:     # eager call: poll, then synchronise
+        if self._stream is None:
+            return word & ~FLAG_PUBLISHED if word & FLAG_PUBLISHED else 0
+        if not word & FLAG_PUBLISHED:        # poll, then synchronise
             deadline, spins = time.perf_counter() + self.POLL_S, 0
             while not word & FLAG_PUBLISHED and time.perf_counter() < deadline:
                 spins += 1
@@ -358,11 +392,10 @@ class FlagTicket:
                 self._stream.synchronize()
                 word = int(self._slot.item()) & 0xffffffff
         if not word & FLAG_PUBLISHED:
-            if self._stream is None:
-                return 0      # captured into a graph that has not been replayed yet: nothing ran
             raise OetrError('the status word of a forward call never reached its flag slot (the call has '
                             'completed): the slot is not device-visible host memory')
-        return word & ~FLAG_PUBLISHED
+        self._value = word & ~FLAG_PUBLISHED
+        return self._value
 
     def release(self):
         """Hand a word captured into a HIP graph back to its reader (the graph was discarded:
@@ -373,20 +406,23 @@ class FlagTicket:
 
 
 class _FlagReader:
-    """Pinned host words for asynchronous status reads, one set per engine: a ring for eager
-    calls (each word is consumed before the ring comes round: the deferred check settles
-    batch i when batch i+2 is submitted - at most two batches, i.e. four words, are pending) and words handed out to calls captured into a HIP
-    graph (every replay rewrites them) until the ticket is released.  Pinning host memory is
-    not allowed while a stream is capturing, so graph words come in pages allocated OUTSIDE
-    capture: one page up front, another whenever an eager call finds the free list short
-    (``reserve_graph_words``) - an engine that re-captures per shape never runs dry as long
-    as it releases the tickets of discarded graphs or makes an eager call in between."""
+    """Pinned host words for the status words of ``*_flagslot`` calls, one set per engine: a ring for
+    eager calls and words handed out to calls captured into a HIP graph (every replay rewrites them)
+    until the ticket is released.  A ring word is zeroed for its next call only once the ticket of its
+    previous call has its value: the module reads every ticket long before the ring comes round (at
+    most seven batches in flight, one word each), a caller that holds more unread tickets than the
+    ring has words waits for the call that stores into the word.  Pinning host memory is not allowed
+    while a stream is capturing, so graph words come in pages allocated OUTSIDE capture: one page up
+    front, another whenever an eager call finds the free list short (``reserve_graph_words``) - an
+    engine that re-captures per shape never runs dry as long as it releases the tickets of discarded
+    graphs or makes an eager call in between."""
 
     SLOTS, GRAPH_PAGE = 16, 16
 
     def __init__(self):
         self._words = torch.zeros(self.SLOTS, dtype=torch.int32).pin_memory()
         self._next = 0
+        self._issued = [None] * self.SLOTS     # ring word -> ticket of the last call handed it
         self._pages = []          # pinned pages of graph words (kept alive here)
         self._free = []           # (page, index) pairs not handed out
         self._dev_base = {}       # pinned block (host address) -> its device address
@@ -417,64 +453,29 @@ class _FlagReader:
             dev = self._dev_base[key] = out.value
         return dev + (slot.data_ptr() - key)
 
-    def publish_slot(self, lib):
-        """Reserve a word for a ``*_flagslot`` forward call: -> (slot, device address, owner, key).
-        Hand all four to :meth:`published` right after the call was enqueued."""
-        capturing = torch.cuda.is_current_stream_capturing()
-        owner = key = None
-        if capturing:
+    def publish(self, lib, device, call):
+        """``call(slot)`` enqueues a ``*_flagslot`` forward call on the current stream of ``device`` that
+        stores its status word at the device address ``slot``: -> that call's :class:`FlagTicket`."""
+        if torch.cuda.is_current_stream_capturing():
             if not self._free:
                 raise OetrError('no free status word for a forward call captured into a HIP graph: release '
                                 'the tickets of discarded graphs (OETR.hip_graph_release) or reserve more '
                                 'outside capture (reserve_graph_words)')
             key = self._free.pop(0)
             slot = self._pages[key[0]][key[1]:key[1] + 1]
-            owner = self
-        else:
-            if len(self._free) < self.GRAPH_PAGE // 2:
-                self.reserve_graph_words(self.GRAPH_PAGE)      # top up while pinning is allowed
-            i = self._next
-            self._next = (self._next + 1) % self.SLOTS
-            slot = self._words[i:i + 1]
-        if not capturing:
-            slot.zero_()      # (host store to pinned memory, before the call is enqueued: the ticket polls for FLAG_PUBLISHED)
-        return slot, self._device_address(lib, slot), owner, key
-
-    def published(self, slot, owner, key, device):
-        """The ticket of a ``*_flagslot`` call just enqueued on the current stream of ``device``."""
-        if torch.cuda.is_current_stream_capturing():
-            # valid once a replay has been synchronised (every replay rewrites the word)
-            return FlagTicket(slot, None, owner, key, published=True)
-        return FlagTicket(slot, None, stream=torch.cuda.current_stream(device), published=True)
-
-    def read(self, lib, fn, handle, ws, device, clear):
-        capturing = torch.cuda.is_current_stream_capturing()
-        owner = key = None
-        if capturing:
-            if not self._free:
-                raise OetrError('no free status word for a read captured into a HIP graph: release the '
-                                'tickets of discarded graphs (OETR.hip_graph_release) or reserve more '
-                                'outside capture (reserve_graph_words)')
-            key = self._free.pop(0)
-            slot = self._pages[key[0]][key[1]:key[1] + 1]
-            owner = self
-        else:
-            if len(self._free) < self.GRAPH_PAGE // 2:
-                self.reserve_graph_words(self.GRAPH_PAGE)      # top up while pinning is allowed
-            i = self._next
-            self._next = (self._next + 1) % self.SLOTS
-            slot = self._words[i:i + 1]
-        if ws is None:
-            slot.zero_()
-            return FlagTicket(slot, None, owner, key)
-        with torch.cuda.device(device):
-            _check(lib, fn(handle, ws.data_ptr(), slot.data_ptr(), int(bool(clear)), _stream(device)),
-                   fn.__name__)
-            if capturing:
-                return FlagTicket(slot, None, owner, key)      # valid once a replay has been synchronised
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(device))
-        return FlagTicket(slot, ev)
+            call(self._device_address(lib, slot))
+            return FlagTicket(slot, owner=self, index=key)
+        if len(self._free) < self.GRAPH_PAGE // 2:
+            self.reserve_graph_words(self.GRAPH_PAGE)      # top up while pinning is allowed
+        i = self._next
+        if self._issued[i] is not None:
+            self._issued[i].value()      # (at once unless the caller holds SLOTS unread tickets)
+        slot = self._words[i:i + 1]
+        slot.zero_()      # (host store to pinned memory, before the call is enqueued: the ticket polls for FLAG_PUBLISHED)
+        call(self._device_address(lib, slot))
+        self._next = (i + 1) % self.SLOTS
+        ticket = self._issued[i] = FlagTicket(slot, stream=torch.cuda.current_stream(device))
+        return ticket
 
 
 def _dev(t, name):
@@ -516,14 +517,7 @@ class HotPathEngine:
         if precision not in self.PRECISIONS:
             raise ValueError(f'precision must be one of {sorted(self.PRECISIONS)}')
         self.precision = precision
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise OetrError('HotPathEngine needs a GPU device')
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        self.device = device
+        self.device = device = _gpu_device(device, 'HotPathEngine')
         missing = [k for k in hot_path_keys() if k not in weights]
         if missing:
             raise KeyError(f'missing hot-path weights: {missing[:4]}...')
@@ -576,6 +570,8 @@ class HotPathEngine:
         self._flag_reader = _FlagReader()
         self._ws_shape = {}     # stream -> geometry the workspace was last carved for
         self._pos_loaded = {}   # stream -> key of the token-major position tables it holds
+        # what the setters below last applied to the handle (0: the library's automatic rule)
+        self._enc_tile_set = self._tail_mode_set = self._dec_split_set = 0
         if enc_tile is not None:
             self.set_encoder_tile(enc_tile)
         if attention not in self.ATTENTIONS:
@@ -587,18 +583,13 @@ class HotPathEngine:
         if os.environ.get('OETR_STATE_PREREDUCE'):      # tuning knob for A/B runs (bench.py, tools/)
             self.set_state_prereduce(int(os.environ['OETR_STATE_PREREDUCE']))
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            try:
-                self.lib.oetr_destroy(h)
-            except Exception:
-                pass
+    __del__ = _destructor('oetr_destroy')
 
     def set_encoder_tile(self, rows):
         """0/None = auto, 32 or 64 token rows per encoder workgroup."""
         _check(self.lib, self.lib.oetr_set_encoder_tile(self._h, int(rows or 0)),
                'oetr_set_encoder_tile')
+        self._enc_tile_set = int(rows or 0)
 
     def _current_ws(self):
         return self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
@@ -616,12 +607,14 @@ class HotPathEngine:
         2 'direct form' (decoder, then the 64-row conv with the taps accumulated in registers, no P
         buffer: large batches; two-plane precisions only)."""
         _check(self.lib, self.lib.oetr_set_tail_mode(self._h, int(mode)), 'oetr_set_tail_mode')
+        self._tail_mode_set = int(mode)
 
     def set_decoder_split(self, k):
         """``oetr_set_decoder_split``: workgroups per image of the decoder chain - 0 automatic (4
         while 2N x 4 workgroups take at most a quarter of the CUs, else 1), 1, or 4 (four
         workgroups exchange five 256-float all-reduces per image inside the launch)."""
         _check(self.lib, self.lib.oetr_set_decoder_split(self._h, int(k)), 'oetr_set_decoder_split')
+        self._dec_split_set = int(k)
 
     def debug_decoder_fault(self, on=True):
         """``oetr_debug_decoder_fault`` (tests): the next four-workgroup decoder launch times out."""
@@ -650,12 +643,6 @@ class HotPathEngine:
         return _query_flags(self.lib, self.lib.oetr_query_flags, self._h, self._current_ws(),
                             self.device, clear)
 
-    def read_flags_async(self, clear=True):
-        """The same without synchronising: a :class:`FlagTicket` whose ``value()`` is the word
-        as it stood behind every call enqueued on the current stream so far."""
-        return self._flag_reader.read(self.lib, self.lib.oetr_read_flags_async, self._h,
-                                      self._current_ws(), self.device, clear)
-
     def check_range(self):
         """Raise if any call since the last check was invalid (clears the word):
         :class:`OetrExchangeError` when the split decoder timed out (after
@@ -680,19 +667,10 @@ class HotPathEngine:
             raise ValueError(
                 f'invalid shape N={n} grids {hf1}x{wf1}, {hf2}x{wf2}: '
                 + self.lib.oetr_last_error().decode())
-        # one workspace per HIP stream: the handle is immutable, so calls on
-        # different streams may overlap as long as their workspaces differ
         key = torch.cuda.current_stream(self.device).cuda_stream
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            old = ws
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-            if old is None:
-                ws[:WORKSPACE_STATUS_BYTES].zero_()       # oetr_workspace_init
-            else:                                         # a sticky flag survives the regrowth
-                ws[:WORKSPACE_STATUS_BYTES].copy_(old[:WORKSPACE_STATUS_BYTES])
-            self._pos_loaded.pop(key, None)
-        if self._ws_shape.get(key) != (n, hf1, wf1, hf2, wf2):   # another carve: tables gone
+        old = self._ws.get(key)
+        ws = _stream_workspace(self._ws, key, self.device, need)
+        if ws is not old or self._ws_shape.get(key) != (n, hf1, wf1, hf2, wf2):   # regrown / another carve: tables gone
             self._ws_shape[key] = (n, hf1, wf1, hf2, wf2)
             self._pos_loaded.pop(key, None)
         return ws
@@ -758,11 +736,9 @@ class HotPathEngine:
             if publish:
                 if stages:
                     raise ValueError('publish=True has no stage outputs (oetr_forward_flagslot)')
-                slot, dptr, owner, key = self._flag_reader.publish_slot(self.lib)
                 fargs = margs if margs is not None else args[:5] + [None, None] + args[5:]
-                _check(self.lib, self.lib.oetr_forward_flagslot(*fargs, dptr, _stream(dev)),
-                       'oetr_forward_flagslot')
-                return (box1, box2), self._flag_reader.published(slot, owner, key, dev)
+                return (box1, box2), self._flag_reader.publish(self.lib, dev, lambda slot: _check(
+                    self.lib, self.lib.oetr_forward_flagslot(*fargs, slot, _stream(dev)), 'oetr_forward_flagslot'))
             if not stages:
                 if margs is not None:
                     _check(self.lib, self.lib.oetr_forward_masked(*margs, None, _stream(dev)),
@@ -843,18 +819,14 @@ class HotPathEngine:
         dev = self.device
         both = torch.empty(2, n, 4, device=dev)   # one [2,n,4] block: what parallel.BoxGatherer sends, without a copy
         box1, box2 = both[0], both[1]
+        args = (self._h, n, hf1, wf1, hf2, wf2, int(img_hw1[0]), int(img_hw1[1]), int(img_hw2[0]),
+                int(img_hw2[1]), ws.data_ptr(), ws.numel(), box1.data_ptr(), box2.data_ptr())
         with torch.cuda.device(dev):
             if publish:
-                slot, dptr, owner, key = self._flag_reader.publish_slot(self.lib)
-                _check(self.lib, self.lib.oetr_forward_tokens_flagslot(
-                    self._h, n, hf1, wf1, hf2, wf2, int(img_hw1[0]), int(img_hw1[1]),
-                    int(img_hw2[0]), int(img_hw2[1]), ws.data_ptr(), ws.numel(),
-                    box1.data_ptr(), box2.data_ptr(), dptr, _stream(dev)), 'oetr_forward_tokens_flagslot')
-                return (box1, box2), self._flag_reader.published(slot, owner, key, dev)
-            _check(self.lib, self.lib.oetr_forward_tokens(
-                self._h, n, hf1, wf1, hf2, wf2, int(img_hw1[0]), int(img_hw1[1]),
-                int(img_hw2[0]), int(img_hw2[1]), ws.data_ptr(), ws.numel(),
-                box1.data_ptr(), box2.data_ptr(), _stream(dev)), 'oetr_forward_tokens')
+                return (box1, box2), self._flag_reader.publish(self.lib, dev, lambda slot: _check(
+                    self.lib, self.lib.oetr_forward_tokens_flagslot(*args, slot, _stream(dev)),
+                    'oetr_forward_tokens_flagslot'))
+            _check(self.lib, self.lib.oetr_forward_tokens(*args, _stream(dev)), 'oetr_forward_tokens')
         return box1, box2
 
     def feature_correlation(self, feat1, feat2, pos1, pos2, mask1=None, mask2=None):
@@ -922,13 +894,7 @@ class NeckEngine:
 
     def __init__(self, weights, device=None):
         self.lib = load_library()
-        device = torch.device('cuda', torch.cuda.current_device()) if device is None \
-            else torch.device(device)
-        if device.type != 'cuda':
-            raise OetrError('NeckEngine needs a GPU device')
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        self.device = device
+        self.device = device = _gpu_device(device, 'NeckEngine')
         missing = [k for k in neck_keys() if k not in weights]
         if missing:
             raise KeyError(f'missing neck weights: {missing}')
@@ -961,27 +927,11 @@ class NeckEngine:
                'oetr_neck_create')
         self._h = handle
         self._ws = {}
-        self._flag_reader = _FlagReader()
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            try:
-                self.lib.oetr_neck_destroy(h)
-            except Exception:
-                pass
+    __del__ = _destructor('oetr_neck_destroy')
 
     def _workspace(self, need):
-        key = torch.cuda.current_stream(self.device).cuda_stream   # one workspace per stream
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            old = ws
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-            if old is None:
-                ws[:WORKSPACE_STATUS_BYTES].zero_()       # oetr_workspace_init
-            else:
-                ws[:WORKSPACE_STATUS_BYTES].copy_(old[:WORKSPACE_STATUS_BYTES])
-        return ws
+        return _stream_workspace(self._ws, torch.cuda.current_stream(self.device).cuda_stream, self.device, need)
 
     def forward(self, backbone_feat):
         """[n,1024,hb,wb] (ResNet layer3 output) -> feat [n,256,hb//2,wb//2]."""
@@ -1054,11 +1004,6 @@ class NeckEngine:
         ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
         return _query_flags(self.lib, self.lib.oetr_neck_query_flags, self._h, ws, self.device, clear)
 
-    def read_flags_async(self, clear=True):
-        ws = self._ws.get(torch.cuda.current_stream(self.device).cuda_stream)
-        return self._flag_reader.read(self.lib, self.lib.oetr_neck_read_flags_async, self._h, ws,
-                                      self.device, clear)
-
     def check_range(self):
         if self.query_flags(clear=True) & FLAG_F16_RANGE:
             raise OetrRangeError('a backbone feature / neck intermediate reached |x| >= 65504 '
@@ -1102,13 +1047,7 @@ class KernelTrace:
         return {names[k].decode(): (launches[k], ms[k]) for k in range(n.value)
                 if launches[k]}
 
-    def __del__(self):
-        t, self._t = getattr(self, '_t', None), None
-        if t:
-            try:
-                self.lib.oetr_trace_destroy(t)
-            except Exception:
-                pass
+    __del__ = _destructor('oetr_trace_destroy', '_t')
 
 
 def sustained_mfma_tflops(device, seconds=1.0):

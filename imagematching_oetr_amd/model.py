@@ -18,6 +18,7 @@ key for key and so that random init follows the reference's
 Their ``forward`` is never called.
 """
 import collections
+import dataclasses
 
 import torch
 import torch.nn as nn
@@ -95,6 +96,17 @@ class _QueryTransformerParams(nn.Module):
                 nn.init.xavier_uniform_(p)
 
 
+@dataclasses.dataclass(slots=True)
+class _Batch:
+    """A submitted batch whose deferred check has not been settled (``OETR._inflight``)."""
+    boxes: tuple            # (box1, box2): views of one [2,n,4] block - its storage identifies the batch
+    tickets: list           # FlagTickets of the batch's status words
+    rerun: object           # rerun(exchange_only) -> the boxes to copy in when the batch tripped; None: unchecked
+    stream: object = None   # side stream of the throughput mode (None: the caller's stream)
+    done: object = None     # event behind the batch on `stream`
+    tainted: bool = False   # enqueued on `stream` behind a failed decoder exchange: re-run as well
+
+
 class OETR(nn.Module):
     """OETR overlap estimator with the MI355X-native hot path."""
 
@@ -169,6 +181,10 @@ class OETR(nn.Module):
         self._neck_key = None
         self._hot_params = None       # cached parameter lists of the identity checks (engine())
         self._neck_params = None
+        self._throughput_applied = None   # what _throughput_policy last applied to _engine (None: nothing yet)
+        self._split_ok = True         # False once OETR_FLAG_EXCHANGE was seen on this engine (settle_exchange)
+        #: A/B knob (bench.py): decoder workgroups per image (1 or 4) on checked routes; None: the automatic rule
+        self.hip_decoder_split = None
         #: THROUGHPUT MODE: batches of consecutive forward_dummy / boxes_from_* calls alternate over this
         #: many HIP streams (one workspace per stream in the engines), so that the kernels of batch
         #: i+1 fill the CUs batch i leaves idle; the engines run their throughput settings (64-token
@@ -186,9 +202,10 @@ class OETR(nn.Module):
         self.hip_queue_depth = 2
         #: the engines' throughput settings without the streams (None: follow hip_streams > 1)
         self.hip_throughput = None
-        self._inflight = collections.deque()   # submitted, not yet settled: (boxes, tickets, rerun, stream, event)
+        self._inflight = collections.deque()   # _Batch records: submitted, not yet settled, oldest first
         self._side_streams = []
         self._submitted = 0
+        self._last_side = None        # side stream of the most recent batch (None: the caller's stream)
         self._graph_tickets = []      # status reads captured into HIP graphs (hip_graph_check)
 
     # ---------------------------------------------------------------- host
@@ -308,8 +325,8 @@ class OETR(nn.Module):
                                          enc_tile=self.hip_enc_tile,
                                          attention=self.hip_attention)
             self._engine_key = key
-            self._split_ok = True     # False once OETR_FLAG_EXCHANGE was seen on this engine (settle_exchange)
-            self._engine._throughput_set = None
+            self._split_ok = True
+            self._throughput_applied = None
         self._throughput_policy(self._engine)
         return self._engine
 
@@ -317,9 +334,9 @@ class OETR(nn.Module):
         """Latency or throughput settings of the engine (``hip_streams`` / ``hip_throughput``):
         the setters mutate the handle, so a change is applied with nothing in flight."""
         want = bool(self.hip_streams > 1 if self.hip_throughput is None else self.hip_throughput)
-        if getattr(eng, '_throughput_set', None) == want:
+        if self._throughput_applied == want:
             return
-        if getattr(eng, '_throughput_set', None) is not None:      # (first call on a fresh engine: nothing in flight yet)
+        if self._throughput_applied is not None:      # (first call on a fresh engine: nothing in flight yet)
             self.hip_flush()
             torch.cuda.synchronize(eng.device)
         two_plane = eng.precision in ('f32_split_f16', 'f32_split_qk16')
@@ -327,7 +344,7 @@ class OETR(nn.Module):
             eng.set_encoder_tile(64 if want else 0)
         if two_plane:
             eng.set_tail_mode(2 if want else 0)
-        eng._throughput_set = want
+        self._throughput_applied = want
 
     def _decoder_policy(self, eng, checked):
         """The four-workgroup decoder chain (``oetr_set_decoder_split``) waits for its peers and
@@ -336,12 +353,11 @@ class OETR(nn.Module):
         acted on; every other route - precisions without a range guard, ``hip_on_overflow =
         'ignore'``, the reference's inner seams - runs one workgroup per image, which waits for
         nobody.  Also off for good once a time-out was seen on this engine."""
-        want = 0 if (checked and getattr(self, '_split_ok', True) and self.hip_streams <= 4) else 1
-        if want == 0 and getattr(self, 'hip_decoder_split', None):     # A/B knob (bench.py): force 1 or 4 on checked routes
+        want = 0 if (checked and self._split_ok and self.hip_streams <= 4) else 1
+        if want == 0 and self.hip_decoder_split:
             want = int(self.hip_decoder_split)
-        if getattr(eng, '_dec_split_set', None) != want:
+        if eng._dec_split_set != want:
             eng.set_decoder_split(want)
-            eng._dec_split_set = want
 
     def exact_engine(self):
         """Exact-fp32 MFMA engine on the same weights: the route taken when an
@@ -481,7 +497,7 @@ class OETR(nn.Module):
     # -------------------------------------- submission, deferred range check
     #: the status-word ring of an engine holds 16 words (hip_engine._FlagReader.SLOTS), the automatic decoder
     #: rule assumes at most four forwards in flight, and the HIP runtime carries four streams without sharing
-    #: a hardware queue: more than eight in flight has no use and would overrun the ring
+    #: a hardware queue: more than eight in flight has no use and would make the ring wait for unread words
     MAX_STREAMS = 8
 
     def _stream_count(self):
@@ -492,7 +508,7 @@ class OETR(nn.Module):
 
     def _inflight_cap(self, k):
         """Batches in flight in the throughput mode: ``hip_queue_depth`` per side stream, at most seven in all
-        (two status words per batch at most, sixteen in an engine's ring), never fewer than one per stream."""
+        (one status word per batch, sixteen in an engine's ring), never fewer than one per stream."""
         return max(k, min(k * max(1, int(self.hip_queue_depth)), 7))
 
     def _streams(self, k):
@@ -518,58 +534,52 @@ class OETR(nn.Module):
             boxes, tickets = enqueue()
             if rerun is None:
                 return boxes
-            return self._range_checked(boxes, tickets, rerun)
-        self._settle_down_to(self._inflight_cap(k) - 1)
-        dev = self.engine().device
-        side = self._streams(k)[self._submitted % k]
-        self._submitted += 1
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            boxes, tickets = enqueue()
-            done = torch.cuda.Event()
-            done.record(side)
-        for t in inputs:                      # allocated on the caller's stream, read on `side`
-            if torch.is_tensor(t) and t.is_cuda:
-                t.record_stream(side)
-        self._inflight.append([boxes, tickets, rerun, side, done, False])
-        self._last_side = side
+            if capturing:
+                # part of a HIP graph: nothing can be examined now, and every replay rewrites the
+                # words - hip_graph_check() reads them after the caller has synchronised a replay
+                self._graph_tickets += tickets
+                return boxes
+            batch = _Batch(boxes, tickets, rerun)
+        else:
+            self._settle_down_to(self._inflight_cap(k) - 1)
+            dev = self.engine().device
+            side = self._streams(k)[self._submitted % k]
+            self._submitted += 1
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                boxes, tickets = enqueue()
+                done = torch.cuda.Event()
+                done.record(side)
+            for t in inputs:                      # allocated on the caller's stream, read on `side`
+                if torch.is_tensor(t) and t.is_cuda:
+                    t.record_stream(side)
+            batch = _Batch(boxes, tickets, rerun, side, done)
+            self._last_side = side
+        # deferred mode: the check runs at a later submit / hip_flush(); immediate mode: now
+        self._inflight.append(batch)
         if not self.hip_defer_check:
             self._settle_down_to(0)
         return boxes
 
     def hip_settled(self, boxes):
-        """True once the deferred check of the batch that returned ``boxes`` (either of its two
-        tensors) has been settled - its values are final (``parallel.BoxGatherer(model=...)``
-        issues a batch's all-gather only then).  Batches settle oldest first: when
-        k x ``hip_queue_depth`` more have been submitted (``hip_streams = k``; two in the latency mode)
-        or at ``hip_flush()``."""
-        return not any(boxes is e[0][0] or boxes is e[0][1] for e in self._inflight)
+        """True once the deferred check of the batch that returned ``boxes`` has been settled - its
+        values are final (``parallel.BoxGatherer(model=...)`` issues a batch's all-gather only then).
+        A batch is found by the storage of its box block, so ``boxes`` may be either of its two
+        tensors or any view of them.  Batches settle oldest first: when k x ``hip_queue_depth`` more
+        have been submitted (``hip_streams = k``; two in the latency mode) or at ``hip_flush()``."""
+        key = boxes.untyped_storage().data_ptr()
+        return not any(b.boxes[0].untyped_storage().data_ptr() == key for b in self._inflight)
 
     def hip_batch_stream(self):
         """The HIP stream the most recently submitted batch was enqueued on (throughput mode:
         one of the side streams; otherwise the caller's current stream) - for work that must be
         ordered right behind that batch without waiting for hip_flush(), e.g. an asynchronous
         all-gather of its boxes."""
-        side = getattr(self, '_last_side', None)
-        if side is not None and self.hip_streams > 1:
-            return side
+        if self._last_side is not None and self.hip_streams > 1:
+            return self._last_side
         return torch.cuda.current_stream(self.engine().device)
 
     # ------------------------------------------------ deferred range check
-    def _range_checked(self, boxes, tickets, rerun):
-        """``boxes`` were enqueued on the caller's stream together with ``tickets``.  Deferred
-        mode: remember them, return at once; the check runs at the next submit / ``hip_flush()``.
-        Immediate mode: wait for the words now."""
-        if torch.cuda.is_current_stream_capturing():
-            # part of a HIP graph: nothing can be examined now, and every replay rewrites the
-            # words - hip_graph_check() reads them after the caller has synchronised a replay
-            self._graph_tickets += tickets
-            return boxes
-        self._inflight.append([boxes, tickets, rerun, None, None, False])
-        if not self.hip_defer_check:
-            self._settle_down_to(0)
-        return boxes
-
     @property
     def _pending(self):
         """The most recently submitted batch whose check has not been settled (None: none)."""
@@ -611,7 +621,6 @@ class OETR(nn.Module):
             else:
                 with torch.cuda.stream(side):
                     self._engine.settle_exchange()
-            self._engine._dec_split_set = 1
 
     def _settle_down_to(self, keep):
         """Settle submitted batches, oldest first, until at most ``keep`` are in flight: the
@@ -619,21 +628,21 @@ class OETR(nn.Module):
         (they have long arrived unless the batch is the newest), a tripped batch is re-run and
         its box tensors are corrected in place."""
         while len(self._inflight) > keep:
-            boxes, tickets, rerun, side, done, tainted = self._inflight.popleft()
-            if side is not None:
-                cur = torch.cuda.current_stream(boxes[0].device)
-                cur.wait_event(done)
-                for b in boxes:
-                    b.record_stream(cur)       # allocated on `side`, consumed on the caller's stream
-            if rerun is not None:
-                self._settle(boxes, tickets, rerun, side, tainted)
+            batch = self._inflight.popleft()
+            if batch.stream is not None:
+                cur = torch.cuda.current_stream(batch.boxes[0].device)
+                cur.wait_event(batch.done)
+                for b in batch.boxes:
+                    b.record_stream(cur)       # allocated on the side stream, consumed on the caller's stream
+            if batch.rerun is not None:
+                self._settle(batch)
 
-    def _settle(self, boxes, tickets, rerun, side=None, tainted=False):
+    def _settle(self, batch):
         flags = 0
-        for t in tickets:
+        for t in batch.tickets:
             flags |= t.value()
-        if not flags & FLAG_INVALID and not tainted:
-            return boxes
+        if not flags & FLAG_INVALID and not batch.tainted:
+            return
         if flags & FLAG_EXCHANGE:
             # a residency time-out of the split decoder, not a property of the inputs: the same
             # precision is submitted again (one workgroup per image); only a range overflow of
@@ -641,18 +650,17 @@ class OETR(nn.Module):
             # on the same stream used the failed call's status block (its call counters are not
             # trustworthy): they are re-run as well when their turn comes.
             for later in self._inflight:
-                if later[3] is side:
-                    later[5] = True
-            self._exchange_failed(side)
-        good = rerun(exchange_only=not flags & FLAG_F16_RANGE)   # may raise under hip_on_overflow == 'raise'
-        for dst, src in zip(boxes, good):
-            dst.copy_(src)          # in place and in stream order: holders of `boxes` see the re-run
-        return boxes
+                if later.stream is batch.stream:
+                    later.tainted = True
+            self._exchange_failed(batch.stream)
+        good = batch.rerun(exchange_only=not flags & FLAG_F16_RANGE)   # may raise under hip_on_overflow == 'raise'
+        for dst, src in zip(batch.boxes, good):
+            dst.copy_(src)          # in place and in stream order: holders of the boxes see the re-run
 
     def hip_flush(self):
         """Complete every submitted batch's deferred range check (``hip_defer_check``), oldest
-        first: waits for those batches' status words only (an event behind an asynchronous 4-byte
-        copy each) and orders the caller's stream behind the side streams of the throughput mode.
+        first: waits for those batches' status words only (published by each batch's last kernel)
+        and orders the caller's stream behind the side streams of the throughput mode.
         A tripped batch is re-run in exact fp32 into the box tensors it returned ('f32') or raises
         ``OetrRangeError`` ('raise').  Called automatically as far as needed when the next batch is
         submitted; call it before consuming the boxes of the LAST batch(es)."""
@@ -668,39 +676,50 @@ class OETR(nn.Module):
         checked = self.hip_on_overflow != 'ignore' and eng.precision in eng.F16_RANGE
         self._decoder_policy(eng, checked)
 
+        def call(e, publish=False):
+            return e.forward(feat1, feat2, pos1, pos2, hw1, hw2, mask1=mask1, mask2=mask2, publish=publish)
+
         def enqueue():
             if not checked:
-                return eng.forward(feat1, feat2, pos1, pos2, hw1, hw2, mask1=mask1, mask2=mask2), []
-            boxes, ticket = eng.forward(feat1, feat2, pos1, pos2, hw1, hw2, mask1=mask1, mask2=mask2,
-                                        publish=True)       # status word published by the last kernel
+                return call(eng), []
+            boxes, ticket = call(eng, publish=True)       # status word published by the last kernel
             return boxes, [ticket]
 
         def rerun(exchange_only=False):
-            if exchange_only:
-                return self._boxes_checked(feat1, feat2, pos1, pos2, hw1, hw2, mask1, mask2)
-            return self._exact_boxes(feat1, feat2, pos1, pos2, hw1, hw2, mask1, mask2)
+            return (self._checked_call if exchange_only else self._exact_call)(call)[0]
         return self._submit(enqueue, rerun if checked else None, [feat1, feat2, pos1, pos2, mask1, mask2])
 
-    def _exact_boxes(self, feat1, feat2, pos1, pos2, hw1, hw2, mask1=None, mask2=None):
+    def _exact_call(self, call):
+        """The route of a call whose GEMM operands overflowed the f16 range: ``OetrRangeError`` under
+        ``hip_on_overflow = 'raise'``, else ``call(engine)`` on the exact-fp32 engine -> (result, engine)."""
         if self.hip_on_overflow == 'raise':
             raise OetrRangeError(
                 f"a GEMM operand reached |x| >= 65504 under hip_precision="
                 f"'{self.hip_precision}'; set hip_precision to 'f32' or 'bf16'")
-        return self.exact_engine().forward(feat1, feat2, pos1, pos2, hw1, hw2, mask1=mask1, mask2=mask2)
+        eng = self.exact_engine()
+        return call(eng), eng
 
-    def _boxes_checked(self, feat1, feat2, pos1, pos2, hw1, hw2, mask1=None, mask2=None):
-        """Immediate (synchronising) form: the re-run route of a tripped fused batch."""
+    def _checked_call(self, call, checked=True):
+        """Immediate (synchronising) check: ``call(engine)`` on the main engine, its status word read at
+        once (``checked``; False: neither read nor a split decoder).  ``OETR_FLAG_EXCHANGE`` (only while
+        the split is still allowed: first time-out) -> ``call`` again at the same precision, one decoder
+        workgroup per image; ``OETR_FLAG_F16_RANGE`` -> :meth:`_exact_call`.  -> (result, engine)."""
         eng = self.engine()
-        self._decoder_policy(eng, checked=True)
-        boxes = eng.forward(feat1, feat2, pos1, pos2, hw1, hw2, mask1=mask1, mask2=mask2)
-        flags = eng.query_flags()
-        if flags & FLAG_EXCHANGE:          # (only while the split is still allowed: first time-out)
+        self._decoder_policy(eng, checked)
+        out = call(eng)
+        flags = eng.query_flags() if checked else 0
+        if flags & FLAG_EXCHANGE:
             self._exchange_failed()
-            boxes = eng.forward(feat1, feat2, pos1, pos2, hw1, hw2, mask1=mask1, mask2=mask2)
+            out = call(eng)
             flags = eng.query_flags()
         if eng.precision in eng.F16_RANGE and flags & FLAG_F16_RANGE:
-            boxes = self._exact_boxes(feat1, feat2, pos1, pos2, hw1, hw2, mask1, mask2)
-        return boxes
+            return self._exact_call(call)
+        return out, eng
+
+    def _boxes_checked(self, feat1, feat2, pos1, pos2, hw1, hw2, mask1=None, mask2=None):
+        """Immediate form of ``boxes_from_features``: the re-run route of a tripped fused batch."""
+        return self._checked_call(lambda e: e.forward(feat1, feat2, pos1, pos2, hw1, hw2, mask1=mask1,
+                                                      mask2=mask2))[0]
 
     def forward(self, data, validation=False):
         """Training-side pipeline of reference ``src/model.py:255-376`` as a FORWARD
@@ -729,23 +748,9 @@ class OETR(nn.Module):
         self.h1, self.w1, self.h2, self.w2 = h1, w1, h2, w2
         with torch.no_grad():
             feat1, feat2, pos1, pos2, hf1, wf1, hf2, wf2 = self.feature_extraction(image1, image2)
-            eng = self.engine()
-            checked = self.hip_on_overflow != 'ignore' and eng.precision in eng.F16_RANGE
-            self._decoder_policy(eng, checked)
-            st = eng.forward(feat1, feat2, pos1, pos2, (h1, w1), (h2, w2), stages=True,
-                             mask1=mask1, mask2=mask2)
-            flags = eng.query_flags() if checked else 0
-            if flags & FLAG_EXCHANGE:      # residency time-out of the split decoder: same precision again
-                self._exchange_failed()
-                st = eng.forward(feat1, feat2, pos1, pos2, (h1, w1), (h2, w2), stages=True,
-                                 mask1=mask1, mask2=mask2)
-                flags = eng.query_flags()
-            if flags & FLAG_F16_RANGE:
-                if self.hip_on_overflow == 'raise':
-                    raise OetrRangeError('a GEMM operand reached |x| >= 65504; use hip_precision "f32"')
-                eng = self.exact_engine()
-                st = eng.forward(feat1, feat2, pos1, pos2, (h1, w1), (h2, w2), stages=True,
-                                 mask1=mask1, mask2=mask2)
+            checked = self.hip_on_overflow != 'ignore' and self.hip_precision in HotPathEngine.F16_RANGE
+            st, eng = self._checked_call(lambda e: e.forward(feat1, feat2, pos1, pos2, (h1, w1), (h2, w2),
+                                                             stages=True, mask1=mask1, mask2=mask2), checked)
             xyxy1, xyxy2, cxywh1, cxywh2 = losses.obtain_overlap_bbox(
                 st['cxy1'], st['tlbr1'], st['cxy2'], st['tlbr2'], (h1, w1), (h2, w2))
             gt1 = data['overlap_box1'][valid].to(xyxy1.device)

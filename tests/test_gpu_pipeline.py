@@ -275,6 +275,11 @@ def test_status_word_is_published_by_the_last_kernel(gpu):
         _, ticket = eng.forward_tokens(2, 5, 6, 5, 6, (160, 192), (160, 192), publish=True)
         assert ticket.value() & pkg.hip_engine.FLAG_F16_RANGE == bit
         assert eng.query_flags(clear=False) == 0
+    # the ring of host words comes round while every ticket is still unread: no ticket reports another call's word
+    ring = pkg.hip_engine._FlagReader.SLOTS
+    tickets = [eng.forward(f1 * 1e6, f2, p1, p2, (256, 256), (160, 224), publish=True)[1]]
+    tickets += [eng.forward(f1, f2, p1, p2, (256, 256), (160, 224), publish=True)[1] for _ in range(ring + 1)]
+    assert [t.value() for t in tickets] == [pkg.hip_engine.FLAG_F16_RANGE] + [0] * (ring + 1)
 
 
 def test_forward_dummy_to_crop_is_one_hip_graph_with_the_default_guard(gpu):
@@ -498,8 +503,9 @@ def test_throughput_mode_is_the_serial_result_bit_for_bit(gpu):
             most = max(most, len(model._inflight))
         assert most == (3 if rnd == 1 else 6), most
         assert model.hip_batch_stream() in model._side_streams
+        assert not model.hip_settled(outs[-1][0][:1])      # a view of an in-flight batch's boxes
         model.hip_flush()
-        assert len(model._inflight) == 0
+        assert len(model._inflight) == 0 and model.hip_settled(outs[-1][0][:1])
         torch.cuda.synchronize()
         for i, (o, r) in enumerate(zip(outs, serial)):
             assert torch.equal(o[0], r[0]) and torch.equal(o[1], r[1]), (rnd, i)

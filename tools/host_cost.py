@@ -1,7 +1,8 @@
 """Host cost of a submitted batch through the module (GPU box): submit into an idle device, hip_streams = 1 and 3,
 plus a cProfile of 300 submits in the throughput mode.  python tools/host_cost.py"""
 import sys, time, cProfile, pstats
-sys.path.insert(0, '/root/repo')
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 import imagematching_oetr_amd as pkg
 torch.set_grad_enabled(False)
