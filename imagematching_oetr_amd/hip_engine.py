@@ -97,6 +97,12 @@ FLAG_EXCHANGE = 2    # OETR_FLAG_EXCHANGE: the split decoder's workgroups were n
 FLAG_INVALID = FLAG_F16_RANGE | FLAG_EXCHANGE   # either bit: that call's outputs are invalid
 FLAG_PUBLISHED = 0x80000000   # OETR_FLAG_PUBLISHED: set in every word a *_flagslot call stores into its slot
 
+# The feature-bank extension (include/oetr_bank.h): a version and an export list of its own
+BANK_ABI_VERSION = 1
+BANK_EXPORTS = ('oetr_bank_abi_version', 'oetr_bank_gather', 'oetr_forward_bank')
+FLAG_INDEX = 4       # OETR_FLAG_INDEX: a pair index was outside its bank (a caller bug: not part of FLAG_INVALID,
+                     # which names what a re-run repairs)
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -273,6 +279,16 @@ def load_library(path=None):
     if lib.oetr_abi_version() != ABI_VERSION:
         raise RuntimeError(f'{p}: ABI version {lib.oetr_abi_version()} != '
                            f'{ABI_VERSION}')
+    # include/oetr_bank.h
+    lib.oetr_bank_abi_version.restype = i
+    lib.oetr_bank_abi_version.argtypes = []
+    bank = [vp, i, vp, vp, i, vp, i]                  # bank1, images, idx1, bank2, images, idx2, n_pairs
+    lib.oetr_bank_gather.restype = i
+    lib.oetr_bank_gather.argtypes = bank + [i, i, vp, vp, vp, vp]
+    lib.oetr_forward_bank.restype = i
+    lib.oetr_forward_bank.argtypes = [vp] + bank + [i] * 8 + [vp, sz, vp, vp, vp, vp]
+    if lib.oetr_bank_abi_version() != BANK_ABI_VERSION:
+        raise RuntimeError(f'{p}: bank ABI version {lib.oetr_bank_abi_version()} != {BANK_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
@@ -827,6 +843,85 @@ class HotPathEngine:
                     self.lib, self.lib.oetr_forward_tokens_flagslot(*args, slot, _stream(dev)),
                     'oetr_forward_tokens_flagslot'))
             _check(self.lib, self.lib.oetr_forward_tokens(*args, _stream(dev)), 'oetr_forward_tokens')
+        return box1, box2
+
+    # ---- bank-fed entry: per-image token rows gathered by index (include/oetr_bank.h) ----
+    def _bank(self, bank, name):
+        """A bank: contiguous float32 [images, L, 256] on the engine's device -> (images, L)."""
+        if not torch.is_tensor(bank) or bank.dim() != 3 or bank.shape[2] != D_MODEL or \
+                bank.dtype != torch.float32 or not bank.is_contiguous() or bank.shape[0] < 1:
+            raise ValueError(f'{name} must be a contiguous float32 [images,L,{D_MODEL}] tensor')
+        if bank.device != self.device:
+            raise OetrError(f'{name} must live on {self.device} (got {bank.device}); the OETR hot path has no '
+                            'CPU implementation')
+        return int(bank.shape[0]), int(bank.shape[1])
+
+    def _bank_index(self, idx, images, n, name):
+        """Pair indices -> int32 device tensor [n].  A device int32 tensor is used as is (nothing is
+        read back: the kernel clamps and reports ``FLAG_INDEX``); a Python sequence / CPU tensor is
+        checked here (``IndexError``) and copied to the device."""
+        if torch.is_tensor(idx) and idx.is_cuda:
+            if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device:
+                raise ValueError(f'{name} on the device must be a contiguous int32 [n] tensor on {self.device}')
+        else:
+            host = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
+            if host.numel() and (int(host.min()) < 0 or int(host.max()) >= images):
+                raise IndexError(f'{name}: index outside the bank (0..{images - 1})')
+            idx = host.to(device=self.device, dtype=torch.int32)
+        if n is not None and idx.numel() != n:
+            raise ValueError(f'{name} holds {idx.numel()} indices, expected {n}')
+        return idx
+
+    def bank_gather(self, bank1, idx1, bank2, idx2, tokens1, tokens2, status_word=None, images=None):
+        """``oetr_bank_gather``: ``tokens1[p] = bank1[idx1[p]]``, ``tokens2[p] = bank2[idx2[p]]`` in one
+        launch.  ``tokens1/2``: contiguous float32 [n*L,256] device tensors; ``status_word``: device
+        tensor whose first 4 bytes take ``FLAG_INDEX``; ``images``: (bank1_images, bank2_images) the
+        kernel is told instead of the tensors' own counts (tests)."""
+        k1, L1 = self._bank(bank1, 'bank1')
+        k2, L2 = self._bank(bank2, 'bank2')
+        if images is not None:
+            k1, k2 = int(images[0]), int(images[1])
+        idx1 = self._bank_index(idx1, k1, None, 'idx1')
+        n = idx1.numel()
+        idx2 = self._bank_index(idx2, k2, n, 'idx2')
+        for t, L, name in ((tokens1, L1, 'tokens1'), (tokens2, L2, 'tokens2')):
+            if tuple(t.shape) != (n * L, D_MODEL) or t.dtype != torch.float32 or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise ValueError(f'{name} must be contiguous float32 [{n * L},{D_MODEL}] on {self.device}')
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.oetr_bank_gather(
+                bank1.data_ptr(), k1, idx1.data_ptr(), bank2.data_ptr(), k2, idx2.data_ptr(), n, L1, L2,
+                tokens1.data_ptr(), tokens2.data_ptr(),
+                status_word.data_ptr() if status_word is not None else None, _stream(self.device)),
+                'oetr_bank_gather')
+        return tokens1, tokens2
+
+    def forward_bank(self, bank1, idx1, bank2, idx2, hf1, wf1, hf2, wf2, img_hw1, img_hw2, publish=False):
+        """``forward_tokens`` on rows gathered from banks by index (``oetr_forward_bank``): pair ``p`` is
+        (``bank1[idx1[p]]``, ``bank2[idx2[p]]``).  ``bank``: contiguous float32 [images, hf*wf, 256] on the
+        engine's device, ``bank2`` may be ``bank1``; ``idx``: int32 device tensor [n] (used as is - a HIP
+        graph replays with what it holds then) or a Python sequence / CPU tensor (checked on the host:
+        ``IndexError``).  The position tables must be in the workspace (``token_buffers`` +
+        ``load_pos_tokens``).  Returns as :meth:`forward_tokens`."""
+        k1, L1 = self._bank(bank1, 'bank1')
+        k2, L2 = self._bank(bank2, 'bank2')
+        if L1 != hf1 * wf1 or L2 != hf2 * wf2:
+            raise ValueError(f'banks hold {L1} / {L2} rows per image, the grids {hf1}x{wf1} / {hf2}x{wf2}')
+        idx1 = self._bank_index(idx1, k1, None, 'idx1')
+        n = idx1.numel()
+        idx2 = self._bank_index(idx2, k2, n, 'idx2')
+        ws = self.workspace(n, hf1, wf1, hf2, wf2)
+        dev = self.device
+        both = torch.empty(2, n, 4, device=dev)   # one [2,n,4] block, as forward_tokens
+        box1, box2 = both[0], both[1]
+        args = (self._h, bank1.data_ptr(), k1, idx1.data_ptr(), bank2.data_ptr(), k2, idx2.data_ptr(), n,
+                hf1, wf1, hf2, wf2, int(img_hw1[0]), int(img_hw1[1]), int(img_hw2[0]), int(img_hw2[1]),
+                ws.data_ptr(), ws.numel(), box1.data_ptr(), box2.data_ptr())
+        with torch.cuda.device(dev):
+            if publish:
+                return (box1, box2), self._flag_reader.publish(self.lib, dev, lambda slot: _check(
+                    self.lib, self.lib.oetr_forward_bank(*args, slot, _stream(dev)), 'oetr_forward_bank'))
+            _check(self.lib, self.lib.oetr_forward_bank(*args, None, _stream(dev)), 'oetr_forward_bank')
         return box1, box2
 
     def feature_correlation(self, feat1, feat2, pos1, pos2, mask1=None, mask2=None):

@@ -207,6 +207,7 @@ class OETR(nn.Module):
         self._submitted = 0
         self._last_side = None        # side stream of the most recent batch (None: the caller's stream)
         self._graph_tickets = []      # status reads captured into HIP graphs (hip_graph_check)
+        self._bank_epoch = 0          # bumped by invalidate_engine(): feature banks filled before are stale
 
     # ---------------------------------------------------------------- host
     def neck(self, x):
@@ -288,6 +289,7 @@ class OETR(nn.Module):
         sub-module (the check walks a cached list of the parameter objects; ``.to()``,
         ``load_state_dict`` and this method refresh it)."""
         self.hip_flush()
+        self._bank_epoch += 1         # feature banks hold what the OLD weights computed (bank.FeatureBank)
         self._engine = self._engine_key = self._engine_f32 = None
         self._neck_engine = self._neck_key = None
         self._hot_params = self._neck_params = None
@@ -493,6 +495,60 @@ class OETR(nn.Module):
             return self._boxes_checked(feat1, feat2, self.pos_encoding(feat1), self.pos_encoding(feat2),
                                        hw1, hw2)
         return self._submit(enqueue, rerun if checked else None, [bb1, bb2] if both is None else [both])
+
+    # ------------------------------------------------------ feature banks
+    def feature_bank(self, image_hw, capacity):
+        """A :class:`~imagematching_oetr_amd.bank.FeatureBank` for up to ``capacity`` images of size
+        ``image_hw`` = (H, W): the trunk and the neck run ONCE per image (``bank.add``), pairs are then
+        given by slot number (:meth:`boxes_from_bank`).  Needs the model on a GPU."""
+        from .bank import FeatureBank
+        return FeatureBank(self, image_hw, capacity)
+
+    @torch.no_grad()
+    def boxes_from_bank(self, bank1, idx1, bank2, idx2):
+        """(box1, box2), each [n,4]: pair ``p`` is (image ``idx1[p]`` of ``bank1``, image ``idx2[p]`` of
+        ``bank2``) - what ``forward_dummy`` returns for those two images, without their trunk and neck
+        (``oetr_forward_bank``: one gather launch assembles the batch from the banks' token rows, then
+        the token-resident hot path).  ``bank2`` may be ``bank1``; ``idx``: sequences of slot numbers as
+        ``bank.add`` returned them, checked on the host (``IndexError``).  The bank-fed sibling of
+        :meth:`boxes_from_backbone`: same deferred range check, ``hip_flush``, ``hip_settled`` and
+        throughput mode.  No masks on this route."""
+        for b in (bank1, bank2):
+            b._check_usable(self)
+        idx = []
+        for b, ix, name in ((bank1, idx1, 'idx1'), (bank2, idx2, 'idx2')):
+            host = torch.as_tensor(ix, dtype=torch.int64).reshape(-1).cpu()
+            if host.numel() and (int(host.min()) < 0 or int(host.max()) >= len(b)):
+                raise IndexError(f'{name}: slot outside the {len(b)} filled slots of the bank')
+            idx.append(host)
+        n = idx[0].numel()
+        if n == 0 or idx[1].numel() != n:
+            raise ValueError(f'idx1 / idx2 must name the same, non-zero number of pairs (got {n}, {idx[1].numel()})')
+        eng = self.engine()
+        (hf1, wf1), (hf2, wf2) = bank1.grid, bank2.grid
+        hw1, hw2 = bank1.image_hw, bank2.image_hw
+        self.h1, self.w1, self.h2, self.w2 = hw1[0], hw1[1], hw2[0], hw2[1]
+        checked = self.hip_on_overflow != 'ignore' and eng.precision in eng.F16_RANGE
+        self._decoder_policy(eng, checked)
+        meta = lambda h, w: torch.empty(1, 1, h, w, device='meta')   # pos_encoding reads sizes only
+        pos1, pos2 = self.pos_encoding(meta(hf1, wf1)), self.pos_encoding(meta(hf2, wf2))
+        rows1, rows2 = bank1.rows, bank2.rows
+        i1 = idx[0].to(device=eng.device, dtype=torch.int32)
+        i2 = idx[1].to(device=eng.device, dtype=torch.int32)
+
+        def enqueue():
+            bufs = eng.token_buffers(n, hf1, wf1, hf2, wf2)
+            eng.load_pos_tokens(bufs, pos1, pos2)
+            if not checked:
+                return eng.forward_bank(rows1, i1, rows2, i2, hf1, wf1, hf2, wf2, hw1, hw2), []
+            boxes, ticket = eng.forward_bank(rows1, i1, rows2, i2, hf1, wf1, hf2, wf2, hw1, hw2, publish=True)
+            return boxes, [ticket]
+
+        def rerun(exchange_only=False):   # the same rows as NCHW features through the immediate route
+            feat1 = rows1[i1.long()].permute(0, 2, 1).reshape(n, -1, hf1, wf1).contiguous()
+            feat2 = rows2[i2.long()].permute(0, 2, 1).reshape(n, -1, hf2, wf2).contiguous()
+            return self._boxes_checked(feat1, feat2, self.pos_encoding(feat1), self.pos_encoding(feat2), hw1, hw2)
+        return self._submit(enqueue, rerun if checked else None, [rows1, rows2, i1, i2])
 
     # -------------------------------------- submission, deferred range check
     #: the status-word ring of an engine holds 16 words (hip_engine._FlagReader.SLOTS), the automatic decoder

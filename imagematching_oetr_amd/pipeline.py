@@ -15,6 +15,10 @@ this module turns a pair *stream* into shape-bucketed batches:
   is what ``model.forward_dummy(image0_i, image1_i)`` returns for that pair alone
   (pairs never interact: no cross-pair term anywhere in reference
   ``src/model.py:229-252``).
+* :func:`forward_pairs_indexed` - the same for a pair list over an image SET: ``images`` once,
+  pairs as ``(i, j)`` index tuples.  Trunk and neck run once per referenced image (a
+  ``bank.FeatureBank`` per image size), the batches are assembled from the banks on the device
+  (``OETR.boxes_from_bank``).
 * :func:`forward_pairs_sharded` - the same over a process group: every bucket is
   split contiguously over the ranks (equal shapes -> equal work), each rank runs
   its share, and ONE padded ``all_gather_into_tensor`` of the ``[n,2,4]`` boxes
@@ -89,6 +93,69 @@ def forward_pairs(model, pairs, max_batch=8):
     res = _run_plan(model, pairs, plan_batches(shapes, max_batch), _model_device(model))
     box0 = torch.stack([res[i][0] for i in range(len(pairs))])
     box1 = torch.stack([res[i][1] for i in range(len(pairs))])
+    return box0, box1
+
+
+def plan_indexed(shapes, pair_index, max_batch):
+    """Work plan of :func:`forward_pairs_indexed`, a pure function of the image sizes and the pair list:
+    ``(banks, batches)``.  ``banks``: ``{(H, W): [image numbers]}`` - one bank per distinct size, holding
+    the images some pair references (unreferenced ones never), in first-referenced order.  ``batches``:
+    ``[((shape_i, shape_j), [pair numbers])]`` - pairs bucketed by the two sizes in first-seen order and
+    cut into chunks of at most ``max_batch``.  ``IndexError`` for a pair that names no image."""
+    if max_batch < 1:
+        raise ValueError('max_batch must be >= 1')
+    banks, seen, keys = {}, set(), []
+    for k, (i, j) in enumerate(pair_index):
+        for m in (i, j):
+            if not 0 <= int(m) < len(shapes):
+                raise IndexError(f'pair {k} = ({i}, {j}) names an image outside 0..{len(shapes) - 1}')
+            if int(m) not in seen:
+                seen.add(int(m))
+                banks.setdefault(tuple(shapes[m]), []).append(int(m))
+        keys.append((tuple(shapes[i]), tuple(shapes[j])))
+    batches = [(key, idx[s:s + max_batch]) for key, idx in bucket_by_shape(keys).items()
+               for s in range(0, len(idx), max_batch)]
+    return banks, batches
+
+
+@torch.no_grad()
+def forward_pairs_indexed(model, images, pair_index, max_batch=8, trunk_batch=16):
+    """Boxes for a pair LIST over an image SET.  ``images``: sequence of ``[H,W,3]`` / ``[1,H,W,3]``
+    float images in [0,1] (any device, mixed sizes); ``pair_index``: sequence of ``(i, j)`` image
+    numbers (``(i, i)`` is legal).  Returns ``(box0, box1)``, each ``[len(pair_index), 4]``, in input
+    order, with the contract of :func:`forward_pairs`: entry ``k`` is what
+    ``model.forward_dummy(images[i_k], images[j_k])`` returns for that pair alone.
+
+    Every referenced image goes through the trunk and the neck ONCE, ``trunk_batch`` images of one
+    size per trunk call, into a feature bank per image size (``model.feature_bank``); the pairs are
+    then run in batches of up to ``max_batch`` straight from the banks (``model.boxes_from_bank``).
+    With every image in r pairs that removes (r-1)/r of the trunk work, which is 95 % of a
+    ``forward_dummy`` call.  All banks live until the call returns: ``(H/32) * (W/32)`` KB per image."""
+    device = _model_device(model)
+    pair_index = [(int(i), int(j)) for i, j in pair_index]
+    shapes = [tuple(_as_batch1(im).shape[1:3]) for im in images]
+    plan, batches = plan_indexed(shapes, pair_index, max_batch)
+    n = len(pair_index)
+    box0, box1 = torch.zeros(n, 4, device=device), torch.zeros(n, 4, device=device)
+    if n == 0:
+        return box0, box1
+    banks, slot = {}, {}
+    for shape, members in plan.items():
+        bank = banks[shape] = model.feature_bank(shape, len(members))
+        for s in range(0, len(members), max(1, trunk_batch)):
+            chunk = members[s:s + max(1, trunk_batch)]
+            batch = torch.cat([_as_batch1(images[m]) for m in chunk]).to(device, non_blocking=True)
+            for m, sl in zip(chunk, bank.add(batch)):
+                slot[m] = sl
+    produced = []
+    for (shape_i, shape_j), idx in batches:
+        b0, b1 = model.boxes_from_bank(banks[shape_i], [slot[pair_index[k][0]] for k in idx],
+                                       banks[shape_j], [slot[pair_index[k][1]] for k in idx])
+        produced.append((idx, b0, b1))
+    model.hip_flush()      # boxes are copied only once settled: a tripped batch is corrected IN PLACE (see forward_pairs_raw)
+    for idx, b0, b1 in produced:
+        di = torch.as_tensor(idx, device=device)
+        box0[di], box1[di] = b0, b1
     return box0, box1
 
 
