@@ -1,0 +1,215 @@
+// Co-visibility boxes (include/oetr_covis.h): the reference's numpy_overlap_box (src/datasets/utils.py:140-202)
+// for a batch of pairs - ground-truth overlap boxes, inlier counts and masks from depth maps, intrinsics and poses.
+//
+// k_covis_warp streams depth map 1: a workgroup of 256 threads takes COVIS_PIX consecutive pixels of one pair (a
+// strip of rows; consecutive lanes read consecutive floats), each thread COVIS_PER_THREAD of them, all loads issued
+// before the arithmetic.  A pixel with depth is un-projected, transformed, projected, truncated and depth-tested in
+// float64 with every operation rounded on its own, in the reference's order (no contraction into FMAs: trunc() and
+// "< 0.5" are discontinuous, and the parity target is a float64 numpy program).  The pair's 37 parameters are
+// wave-uniform loads.  Per thread: eight box bounds and a count in registers, all kept as MAXIMA of non-negative codes
+// (a minimum m is kept as SIDE - m, a maximum M as M + 1; 0 = nothing seen), so that the all-zero accumulator a memset
+// leaves is the neutral element.  Wave reduction by __shfl_xor over 64 lanes, one LDS step per workgroup, then one set
+// of integer atomicMax / atomicAdd per workgroup that saw an inlier: integer atomics commute, the result does not
+// depend on arrival order.  k_covis_finish (one thread per pair) decodes the accumulators into float32 boxes, the
+// valid byte and the count.  Masks are plain byte stores of 1 into memory the call cleared.
+#include <string>
+
+#include "../../include/oetr_covis.h"
+#include "common.h"
+
+namespace oetr {
+
+constexpr int COVIS_THREADS = 256;
+constexpr int COVIS_PER_THREAD = 8;
+constexpr int COVIS_PIX = COVIS_THREADS * COVIS_PER_THREAD;      // pixels per workgroup
+constexpr int COVIS_ACC = 16;                                    // int32 per pair in the workspace (64 B; 9 used)
+constexpr int SIDE = OETR_COVIS_MAX_SIDE;
+enum { A_MINU, A_MINV, A_MAXU, A_MAXV, A_MINI, A_MINJ, A_MAXI, A_MAXJ, A_COUNT, A_USED };
+
+// grid: x = blocks of COVIS_PIX pixels of one map, y = pair
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __restrict__ depth1,
+                                                              const float* __restrict__ depth2,
+                                                              const double* __restrict__ params, int H, int W,
+                                                              int* __restrict__ acc, uint8_t* __restrict__ mask1,
+                                                              uint8_t* __restrict__ mask2) {
+#pragma clang fp contract(off)
+  const int pair = blockIdx.y;
+  const int n_pix = H * W;                                        // <= 2^26
+  const size_t map = (size_t)pair * (size_t)n_pix;
+  const float* d1 = depth1 + map;
+  const float* d2 = depth2 + map;
+  const int first = (int)blockIdx.x * COVIS_PIX + (int)threadIdx.x;
+
+  float z[COVIS_PER_THREAD];
+#pragma unroll
+  for (int k = 0; k < COVIS_PER_THREAD; ++k) {
+    const int idx = first + k * COVIS_THREADS;
+    z[k] = idx < n_pix ? d1[idx] : 0.0f;
+  }
+
+  const double* P = params + (size_t)pair * OETR_COVIS_PARAM_DOUBLES;   // wave-uniform
+  const double fx = P[16], fy = P[17], cx = P[18], cy = P[19];
+  const double b1r = P[29], b1c = P[30], r1r = P[31], r1c = P[32];
+  const double b2r = P[33], b2c = P[34], r2r = P[35], r2c = P[36];
+
+  int best[A_USED];
+#pragma unroll
+  for (int a = 0; a < A_USED; ++a) best[a] = 0;
+
+#pragma unroll
+  for (int k = 0; k < COVIS_PER_THREAD; ++k) {
+    if (!(z[k] > 0.0f)) continue;                                 // no depth (0, negative, NaN) or past the map
+    const int idx = first + k * COVIS_THREADS;
+    const int v = idx / W, u = idx - v * W;
+    const double Z = (double)z[k];
+    const double x = ((double)u + b1c + 0.5) / r1c;
+    const double y = ((double)v + b1r + 0.5) / r1r;
+    const double X = (x - cx) * (Z / fx);
+    const double Y = (y - cy) * (Z / fy);
+    double q[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) q[r] = ((P[4 * r] * X + P[4 * r + 1] * Y) + P[4 * r + 2] * Z) + P[4 * r + 3];
+    // a rigid T has the last row (0, 0, 0, 1) and q[3] is exactly 1: x / 1.0 is x for every x (inf and NaN too), so
+    // the three divisions are skipped without changing a bit of the result
+    double Xc = q[0], Yc = q[1], Zc = q[2];
+    if (q[3] != 1.0) { Xc = q[0] / q[3]; Yc = q[1] / q[3]; Zc = q[2] / q[3]; }
+    double h[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) h[r] = (P[20 + 3 * r] * Xc + P[21 + 3 * r] * Yc) + P[22 + 3 * r] * Zc;
+    const double u2 = (h[0] / h[2]) * r2c - b2c - 0.5;
+    const double v2 = (h[1] / h[2]) * r2r - b2r - 0.5;
+    // trunc(u2) in [0, W) <=> -1 < u2 < W (false for NaN; +-inf and anything beyond int are outside)
+    if (!(u2 > -1.0 && u2 < (double)W && v2 > -1.0 && v2 < (double)H)) continue;
+    const int i = (int)u2, j = (int)v2;                           // towards zero; 0 <= i < W, 0 <= j < H
+    const double Z2 = (double)d2[(size_t)j * W + i];
+    if (!(fabs(Zc - Z2) < 0.5)) continue;
+    best[A_MINU] = max(best[A_MINU], SIDE - u);
+    best[A_MINV] = max(best[A_MINV], SIDE - v);
+    best[A_MAXU] = max(best[A_MAXU], u + 1);
+    best[A_MAXV] = max(best[A_MAXV], v + 1);
+    best[A_MINI] = max(best[A_MINI], SIDE - i);
+    best[A_MINJ] = max(best[A_MINJ], SIDE - j);
+    best[A_MAXI] = max(best[A_MAXI], i + 1);
+    best[A_MAXJ] = max(best[A_MAXJ], j + 1);
+    best[A_COUNT] += 1;
+    if (mask1) {
+      mask1[map + (size_t)idx] = 1;
+      mask2[map + (size_t)j * W + i] = 1;
+    }
+  }
+
+  // wave: butterfly over 64 lanes
+#pragma unroll
+  for (int a = 0; a < A_USED; ++a) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const int other = __shfl_xor(best[a], off, 64);
+      best[a] = a == A_COUNT ? best[a] + other : max(best[a], other);
+    }
+  }
+  // workgroup: one LDS step, then one atomic per accumulator
+  __shared__ int part[COVIS_THREADS / 64][A_USED];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < A_USED; ++a) part[wave][a] = best[a];
+  }
+  __syncthreads();
+  if (threadIdx.x < A_USED) {
+    const int a = threadIdx.x;
+    int r = part[0][a];
+    int n = part[0][A_COUNT];
+    for (int w = 1; w < COVIS_THREADS / 64; ++w) {
+      r = a == A_COUNT ? r + part[w][a] : max(r, part[w][a]);
+      n += part[w][A_COUNT];
+    }
+    if (n > 0) {
+      int* dst = acc + (size_t)pair * COVIS_ACC + a;
+      if (a == A_COUNT) atomicAdd(dst, r); else atomicMax(dst, r);
+    }
+  }
+}
+
+// one thread per pair
+__global__ void k_covis_finish(const int* __restrict__ acc, int n_pairs, float* __restrict__ box1,
+                               float* __restrict__ box2, uint8_t* __restrict__ valid, int32_t* __restrict__ count) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  const int* a = acc + (size_t)p * COVIS_ACC;
+  const int n = a[A_COUNT];
+  const bool ok = n > 0;
+  float* b1 = box1 + 4 * (size_t)p;
+  float* b2 = box2 + 4 * (size_t)p;
+  b1[0] = ok ? (float)(SIDE - a[A_MINU]) : 0.0f;
+  b1[1] = ok ? (float)(SIDE - a[A_MINV]) : 0.0f;
+  b1[2] = ok ? (float)(a[A_MAXU] - 1) : 0.0f;
+  b1[3] = ok ? (float)(a[A_MAXV] - 1) : 0.0f;
+  b2[0] = ok ? (float)(SIDE - a[A_MINI]) : 0.0f;
+  b2[1] = ok ? (float)(SIDE - a[A_MINJ]) : 0.0f;
+  b2[2] = ok ? (float)(a[A_MAXI] - 1) : 0.0f;
+  b2[3] = ok ? (float)(a[A_MAXJ] - 1) : 0.0f;
+  valid[p] = ok ? 1 : 0;
+  if (count) count[p] = n;
+}
+
+namespace {
+
+oetr_status covis_fail(oetr_status st, const std::string& msg) {
+  return (oetr_status)set_last_error(st, ("oetr_covis_boxes: " + msg).c_str());
+}
+
+oetr_status covis_hip(hipError_t e, const char* what) {
+  return e == hipSuccess ? OETR_OK : covis_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+}  // namespace
+}  // namespace oetr
+
+using namespace oetr;
+
+extern "C" {
+
+int oetr_covis_abi_version(void) { return OETR_COVIS_ABI_VERSION; }
+
+size_t oetr_covis_workspace_bytes(int n_pairs) {
+  return n_pairs > 0 ? (size_t)n_pairs * COVIS_ACC * sizeof(int) : 0;
+}
+
+oetr_status oetr_covis_boxes(const float* depth1, const float* depth2, const double* params, int n_pairs,
+                             int H, int W, void* workspace, size_t workspace_bytes, float* box1, float* box2,
+                             uint8_t* valid, int32_t* count, uint8_t* mask1, uint8_t* mask2, void* stream) {
+  if (!depth1 || !depth2 || !params) return covis_fail(OETR_ERR_BAD_ARG, "NULL depth / parameter pointer");
+  if (!box1 || !box2 || !valid) return covis_fail(OETR_ERR_BAD_ARG, "NULL box / valid output");
+  if ((mask1 == nullptr) != (mask2 == nullptr))
+    return covis_fail(OETR_ERR_BAD_ARG, "mask1 and mask2 must both be NULL or both be set");
+  if (n_pairs <= 0) return covis_fail(OETR_ERR_BAD_ARG, "need n_pairs > 0");
+  if (H < 1 || W < 1 || H > SIDE || W > SIDE)
+    return covis_fail(OETR_ERR_BAD_SHAPE, "need 1 <= H, W <= " + std::to_string(SIDE));
+  const size_t need = oetr_covis_workspace_bytes(n_pairs);
+  if (!workspace || workspace_bytes < need)
+    return covis_fail(OETR_ERR_BAD_ARG, "workspace NULL or smaller than oetr_covis_workspace_bytes(n_pairs) = " +
+                                            std::to_string(need));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t n_pix = (size_t)H * W;
+  int* acc = static_cast<int*>(workspace);
+  if (oetr_status rc = covis_hip(hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)")) return rc;
+  if (mask1) {
+    if (oetr_status rc = covis_hip(hipMemsetAsync(mask1, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask1)")) return rc;
+    if (oetr_status rc = covis_hip(hipMemsetAsync(mask2, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask2)")) return rc;
+  }
+  constexpr int max_pairs = 65535;                                // the grid's y extent: more pairs, more launches
+  const unsigned blocks = (unsigned)((n_pix + COVIS_PIX - 1) / COVIS_PIX);
+  for (int p0 = 0; p0 < n_pairs; p0 += max_pairs) {
+    const int n = n_pairs - p0 < max_pairs ? n_pairs - p0 : max_pairs;
+    const size_t off = (size_t)p0 * n_pix;
+    hipLaunchKernelGGL(k_covis_warp, dim3(blocks, (unsigned)n), dim3(COVIS_THREADS), 0, s, depth1 + off,
+                       depth2 + off, params + (size_t)p0 * OETR_COVIS_PARAM_DOUBLES, H, W,
+                       acc + (size_t)p0 * COVIS_ACC, mask1 ? mask1 + off : nullptr, mask2 ? mask2 + off : nullptr);
+    if (oetr_status rc = covis_hip(hipGetLastError(), "k_covis_warp")) return rc;
+  }
+  hipLaunchKernelGGL(k_covis_finish, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, acc, n_pairs, box1,
+                     box2, valid, count);
+  return covis_hip(hipGetLastError(), "k_covis_finish");
+}
+
+}  // extern "C"

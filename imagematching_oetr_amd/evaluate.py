@@ -1,0 +1,94 @@
+"""Recall of ``forward_dummy``'s boxes against ground-truth overlap boxes: the reference's
+``evaluate_dummy`` (``src/utils/validation.py:111-146``, ``_recalls`` ``:20-25``).
+
+For every batch the model predicts two boxes per pair; each is scored against the pair's
+ground-truth co-visibility box by aligned IoU (or by the overlap's share of the ground-truth box,
+``oiou``).  All ``2N`` values count - pairs without any co-visible pixel (a zero ground-truth box)
+included, as in the reference - and the recall at a threshold is the share of values at or above it.
+
+The ground truth comes from the batch (``overlap_box1`` / ``overlap_box2``, what the reference's
+dataset emits) or is computed on the device from depth maps, intrinsics and poses
+(``covis.overlap_boxes_from_batch``).
+"""
+import numpy as np
+import torch
+
+from .covis import overlap_boxes_from_batch
+from .losses import bbox_iou_aligned, bbox_oiou
+from .pipeline import _model_device
+
+DEFAULT_IOU_THRS = np.arange(0.5, 0.96, 0.05)
+
+
+def count_recalls(ious, iou_thrs):
+    """``ious`` [M] (any float dtype, any device) -> int64 [len(iou_thrs)] on that device: how many
+    values are ``>= thr``, compared in float64 as numpy compares a float32 array with a float64
+    threshold.  No host read."""
+    thrs = torch.as_tensor(np.asarray(iou_thrs, dtype=np.float64), device=ious.device)
+    return (ious.to(torch.float64)[:, None] >= thrs[None, :]).sum(0)
+
+
+@torch.no_grad()
+def evaluate_dummy(model, batches, iou_thrs=DEFAULT_IOU_THRS, oiou=False, gt='auto', logger=None):
+    """``batches``: an iterable of dataset-style dicts with ``image1`` / ``image2`` ``[N,H,W,3]`` in
+    [0,1] and the ground truth: ``overlap_box1`` / ``overlap_box2`` ``[N,4]`` (``gt='batch'``), or
+    ``depth1``, ``intrinsics1``, ``pose1``, ``bbox1``, ``ratio1`` and the same for ``2`` (``gt='depth'``:
+    the boxes are computed on the device).  ``gt='auto'`` takes the batch's boxes where it has them.
+
+    Returns ``{'recalls': ndarray[len(iou_thrs)], 'n': number of scored boxes (2 per pair),
+    'mean_iou': float (a NaN score - ``oiou`` against a zero box - counts as 0, as it fails every
+    threshold), 'n_valid_pairs': int}`` - pairs whose ground truth is valid: ``overlap_valid``
+    where the ground truth carries it (always for ``gt='depth'``), otherwise pairs with a non-zero
+    ground-truth box.  With a ``logger`` the reference's table (R0.5, R0.75, R0.9: entries 0, 5, 8 of
+    the default thresholds) is logged.
+
+    Boxes are scored only once SETTLED: ``forward_dummy`` defers its range check
+    (``OETR.hip_defer_check``) and corrects a tripped batch in place later, so the batches' box
+    tensors are kept and scored after one ``model.hip_flush()`` at the end, as
+    ``pipeline.forward_pairs_raw`` does.  IoUs and the per-threshold counts stay on the device; the
+    whole evaluation reads the device once."""
+    if gt not in ('auto', 'batch', 'depth'):
+        raise ValueError(f"gt must be 'auto', 'batch' or 'depth', got {gt!r}")
+    thrs = np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    device = _model_device(model)
+    produced = []          # (gt_box1, gt_box2, valid or None, pred_box1, pred_box2) per batch
+    for batch in batches:
+        image1 = batch['image1'].to(device, non_blocking=True)
+        image2 = batch['image2'].to(device, non_blocking=True)
+        pred1, pred2 = model.forward_dummy(image1, image2)
+        has_boxes = 'overlap_box1' in batch and 'overlap_box2' in batch
+        if gt == 'batch' and not has_boxes:
+            raise KeyError("gt='batch': the batch has no overlap_box1 / overlap_box2")
+        if gt == 'depth' or not has_boxes:
+            truth = overlap_boxes_from_batch(batch)
+        else:
+            truth = batch
+        box = lambda t: torch.as_tensor(t).to(device=pred1.device, dtype=torch.float32, non_blocking=True)
+        valid = truth.get('overlap_valid')
+        if valid is not None:
+            valid = torch.as_tensor(valid).to(pred1.device, non_blocking=True).reshape(-1) != 0
+        produced.append((box(truth['overlap_box1']), box(truth['overlap_box2']), valid, pred1, pred2))
+    flush = getattr(model, 'hip_flush', None)
+    if flush is not None:
+        flush()
+    if not produced:
+        return {'recalls': np.zeros(thrs.size), 'n': 0, 'mean_iou': float('nan'), 'n_valid_pairs': 0}
+    score = bbox_oiou if oiou else bbox_iou_aligned
+    ious, n_valid = [], 0
+    for gt1, gt2, valid, pred1, pred2 in produced:
+        ious += [score(gt1, pred1), score(gt2, pred2)]
+        if valid is None:
+            valid = (gt1 != 0).any(1) | (gt2 != 0).any(1)
+        n_valid = n_valid + valid.sum()
+    ious = torch.cat(ious)
+    n = int(ious.numel())
+    # counts, the IoU sum and the valid pairs in ONE float64 tensor (exact for these integers): one read
+    packed = torch.cat([count_recalls(ious, thrs).to(torch.float64), ious.to(torch.float64).nansum()[None],
+                        n_valid.to(torch.float64)[None]]).cpu().numpy()
+    recalls = packed[:thrs.size] / float(n)
+    if logger is not None and thrs.size > 8:
+        logger.info('Validation results:')
+        logger.info('Recalls\t R0.5\t R0.75\t R0.9\t')
+        logger.info('Values\t {:.5f}\t {:.5f}\t {:.5f}\t'.format(recalls[0], recalls[5], recalls[8]))
+    return {'recalls': recalls, 'n': n, 'mean_iou': float(packed[thrs.size] / n),
+            'n_valid_pairs': int(packed[thrs.size + 1])}

@@ -103,6 +103,11 @@ BANK_EXPORTS = ('oetr_bank_abi_version', 'oetr_bank_gather', 'oetr_forward_bank'
 FLAG_INDEX = 4       # OETR_FLAG_INDEX: a pair index was outside its bank (a caller bug: not part of FLAG_INVALID,
                      # which names what a re-run repairs)
 
+# The co-visibility extension (include/oetr_covis.h): likewise
+COVIS_ABI_VERSION = 1
+COVIS_EXPORTS = ('oetr_covis_abi_version', 'oetr_covis_workspace_bytes', 'oetr_covis_boxes')
+COVIS_PARAM_DOUBLES = 40   # OETR_COVIS_PARAM_DOUBLES
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -289,6 +294,16 @@ def load_library(path=None):
     lib.oetr_forward_bank.argtypes = [vp] + bank + [i] * 8 + [vp, sz, vp, vp, vp, vp]
     if lib.oetr_bank_abi_version() != BANK_ABI_VERSION:
         raise RuntimeError(f'{p}: bank ABI version {lib.oetr_bank_abi_version()} != {BANK_ABI_VERSION}')
+    # include/oetr_covis.h
+    lib.oetr_covis_abi_version.restype = i
+    lib.oetr_covis_abi_version.argtypes = []
+    lib.oetr_covis_workspace_bytes.restype = sz
+    lib.oetr_covis_workspace_bytes.argtypes = [i]
+    lib.oetr_covis_boxes.restype = i
+    # depth1, depth2, params, n_pairs, H, W, workspace, bytes, box1, box2, valid, count, mask1, mask2, stream
+    lib.oetr_covis_boxes.argtypes = [vp, vp, vp, i, i, i, vp, sz] + [vp] * 7
+    if lib.oetr_covis_abi_version() != COVIS_ABI_VERSION:
+        raise RuntimeError(f'{p}: covis ABI version {lib.oetr_covis_abi_version()} != {COVIS_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
