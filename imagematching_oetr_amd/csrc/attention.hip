@@ -207,14 +207,11 @@ hipError_t launch_full_attention(const float* q, const float* k, const float* v,
 //   6.5 -> 4.5 VALU instructions per score element (exp, row sum, half a max3, convert, residual, convert).
 // P is still split into two planes like every other operand: a single f16 plane for P (VERDICT r5's suggestion) was
 // measured first - 3e-5 .. 8e-5 against the fp64 oracle where the goldens allow 5e-6, for 13 % of launch time
-// (profiles/r6_full_attention_p1plane.txt; the -DOETR_FA_P1PLANE build keeps the experiment reproducible).
+// (profiles/r6_full_attention_p1plane.txt).
 constexpr int FA_KT = 64;            // keys per tile
 constexpr int FA_KP = 40;            // halves per K row (32 d + 8): conflict-free ds_read_b128
 constexpr int FA_VP = FA_KT + 8;     // halves per V^T row (64 key slots + 8): 9 x 16 B, conflict-free
-#ifndef OETR_FA_WAVES
-#define OETR_FA_WAVES 8
-#endif
-constexpr int FA_WAVES = OETR_FA_WAVES;   // waves per workgroup, 32 queries each
+constexpr int FA_WAVES = 8;          // waves per workgroup, 32 queries each
 struct FaTile {
   _Float16 Kh[FA_KT * FA_KP], Kl[FA_KT * FA_KP];   // K: hi, UNSCALED lo (split2u)
   _Float16 Vh[HD * FA_VP], Vl[HD * FA_VP];   // [d][key slot]
@@ -452,14 +449,9 @@ __global__ __launch_bounds__(64 * FA_WAVES) void k_full_attention_split(const fl
     for (int ks = 0; ks < 4; ++ks) {
       const f32x4 ah = *reinterpret_cast<const f32x4*>(B.Vh + col * FA_VP + 16 * ks + 8 * half);
       const f32x4 al = *reinterpret_cast<const f32x4*>(B.Vl + col * FA_VP + 16 * ks + 8 * half);
-#ifdef OETR_FA_P1PLANE   // experiment (profiles/r6_full_attention_p1plane.txt): P as ONE f16 plane, V split
-      o = mma16<GM_SPLIT>(ah, ph[ks], o);
-      oc = mma16<GM_SPLIT>(al, ph[ks], oc);
-#else
       o = mma16<GM_SPLIT>(ah, ph[ks], o);     // V_hi . P'_hi
       oc = mma16<GM_SPLIT>(al, ph[ks], oc);   // V_lo (x 2^11) . P'_hi
       o = mma16<GM_SPLIT>(ah, pl[ks], o);     // V_hi . P'_lo (unscaled lo plane: the same scale)
-#endif
     }
   };
 

@@ -21,8 +21,14 @@ constexpr float LN_EPS = 1e-5f;
 constexpr float ATTN_EPS = 1e-6f;
 constexpr int MAX_TOKENS = 10000;  // NECK.MAX_SHAPE 100x100 (reference default.py:25-28)
 
-// Ablation switches for timing attribution (tools/ablate.sh builds a second
-// library with -DOETR_ABLATE; the shipped build compiles them out).
+// Build-time switches: these four, and nothing else, select code in csrc/ (every tuning value is a constant beside
+// its use).  An instrumented library is a variant build, `tools/variants.sh <name> "<flags>"` (csrc/Makefile: variant).
+//   OETR_ABLATE        timing attribution (tools/ablate_run.py): ABL() and the cumulative PHASE_STAMP below
+//   OETR_PHASE_TIMING  phase stamps, 1 = shader clock (tools/phase_timing*.py), 3 = real time (tools/launch_boundary.py)
+//   OETR_SOAK_AMP      hazard amplifiers of liboetr_hip_soak.so (csrc/Makefile; tests/test_gpu_determinism.py)
+//   OETR_SPLIT_STATE   emergency switch of the split-f16 linear-attention state (encoder.hip)
+
+// Ablation switches for timing attribution (-DOETR_ABLATE; the shipped build compiles them out).
 #ifdef OETR_ABLATE
 #define ABL(flags, bit) (((flags) & (bit)) != 0)
 #else
@@ -35,12 +41,6 @@ constexpr int MAX_TOKENS = 10000;  // NECK.MAX_SHAPE 100x100 (reference default.
 // phases up to n under real conditions (launch, loads and barriers included).
 #if defined(OETR_ABLATE)
 #define PHASE_STAMP(p, idx) do { if (((p).dbg >> 16) == (idx) + 1) return; } while (0)
-#elif defined(OETR_PHASE_TIMING) && OETR_PHASE_TIMING == 2   // per WAVE, workgroups 0..15 (tools/wave_skew64.py)
-#define PHASE_STAMP(p, idx)                                                              \
-  do {                                                                                   \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 16 && (p).tbuf)                          \
-      (p).tbuf[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 16 + (idx)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
 #elif defined(OETR_PHASE_TIMING) && OETR_PHASE_TIMING == 3   // REAL time (s_memrealtime, 100 MHz): launch boundaries, clock (tools/launch_boundary.py)
 #define PHASE_STAMP(p, idx)                                                              \
   do {                                                                                   \
@@ -75,25 +75,17 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // fragments and partial states per encoder launch at 8 pairs = ~3 us exposed at each of the eight
 // boundaries).  An sc1 store leaves L2 as it is issued, under the kernel's own compute, and the
 // boundary is down to its fixed part; the price is that the line is dropped from L2, so the next
-// launch reads it from the Infinity Cache instead.  OETR_WT is the set of encoder outputs stored
-// this way (bit 0: residual rows x, 1: phi(Q) fragments, 2: partial linear-attention states);
+// launch reads it from the Infinity Cache instead.  All three encoder outputs are stored
+// this way (residual rows x, phi(Q) fragments, partial linear-attention states);
 // same values to the same addresses either way - results are bit-identical.  Measured
 // (profiles/r4_wt_stores.txt, one-process A/B, serial step): all three -1.8 % at 32 pairs @1024x1024,
 // -1.4 % at 8 pairs 640x640 vs 1280x1280, -0.5 % at 8 pairs @640x640, +0.7 % at one pair; overlapped
 // throughput within the noise (+0.8 % at 8 pairs @640x640) - i.e. the flush is a small part of what a
 // boundary costs here; shipped because it is free and never worse beyond the noise.
-#ifndef OETR_WT
-#define OETR_WT 7
-#endif
-template <bool WT>
 __device__ __forceinline__ void store16(float* base_uniform, unsigned byte_off, const f32x4& v) {
-  if constexpr (WT) {
-    typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base_uniform, 0, 0x7fffffff, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), rs, (int)byte_off, 0, 16 /* sc1 */);
-  } else {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(base_uniform) + byte_off) = v;
-  }
+  typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base_uniform, 0, 0x7fffffff, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), rs, (int)byte_off, 0, 16 /* sc1 */);
 }
 
 // Arithmetic of the GEMM-shaped stages (values == oetr_dtype in include/oetr_hip.h).
@@ -127,37 +119,11 @@ constexpr int site_mfmas(int s) { return s == SITE_FULL ? 3 : s == SITE_HI ? 1 :
 //   Q, K and the decoder's K projection tolerate f16 operands (phi(Q) enters numerator and
 //   normaliser alike, K only through sums over all source tokens); V, merge, both MLP GEMMs and
 //   the attention contractions do not (each alone: 1 - IoU = 3e-3 .. 3e-2).
-// Policy 0 = every site fp32-class.  The OETR_SITE_* macros exist for the per-site drift study
-// (variant builds of the library), not for shipping.
-#ifndef OETR_SITE_Q
-#define OETR_SITE_Q SITE_FULL
-#endif
-#ifndef OETR_SITE_K
-#define OETR_SITE_K SITE_FULL
-#endif
-#ifndef OETR_SITE_V
-#define OETR_SITE_V SITE_FULL
-#endif
-#ifndef OETR_SITE_MERGE
-#define OETR_SITE_MERGE SITE_FULL
-#endif
-#ifndef OETR_SITE_MLP1
-#define OETR_SITE_MLP1 SITE_FULL
-#endif
-#ifndef OETR_SITE_MLP2
-#define OETR_SITE_MLP2 SITE_FULL
-#endif
-#ifndef OETR_SITE_DEC_K
-#define OETR_SITE_DEC_K SITE_FULL
-#endif
-#ifndef OETR_SITE_DEC_V
-#define OETR_SITE_DEC_V SITE_FULL
-#endif
+// Policy 0 = every site fp32-class.
 template <int POL> struct SitePolicy;
 template <> struct SitePolicy<0> {
-  static constexpr int Q = OETR_SITE_Q, K = OETR_SITE_K, V = OETR_SITE_V, MERGE = OETR_SITE_MERGE,
-                       MLP1 = OETR_SITE_MLP1, MLP2 = OETR_SITE_MLP2, DEC_K = OETR_SITE_DEC_K,
-                       DEC_V = OETR_SITE_DEC_V;
+  static constexpr int Q = SITE_FULL, K = SITE_FULL, V = SITE_FULL, MERGE = SITE_FULL, MLP1 = SITE_FULL,
+                       MLP2 = SITE_FULL, DEC_K = SITE_FULL, DEC_V = SITE_FULL;
 };
 template <> struct SitePolicy<1> {   // OETR_DTYPE_F32_SPLIT_QK16
   static constexpr int Q = SITE_HI, K = SITE_HI, V = SITE_FULL, MERGE = SITE_FULL, MLP1 = SITE_FULL,
@@ -365,12 +331,9 @@ __device__ __forceinline__ void gemm_mma(const GemmRegs<NT, U>& r, f32x16 (&acc)
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(r.a[u][j], r.b[u][t][j], acc[t], 0, 0, 0);
 }
 
-#ifndef OETR_GEMM_U
-#define OETR_GEMM_U 4
-#endif
 // (Fetching a GEMM's first weight chunk one phase early was measured and is a
 // loss: +7 us per encoder launch - tools/variants A/B - so every GEMM starts cold.)
-template <int K, int NT, int U = OETR_GEMM_U>
+template <int K, int NT, int U = 4>
 __device__ __forceinline__ void gemm_rows32(const float* __restrict__ A, int lda,
                                             const f32x4* __restrict__ Wp, int nt0,
                                             int lane, f32x16 (&acc)[NT], int dbg = 0) {
@@ -557,24 +520,19 @@ __device__ __forceinline__ void split2u(float a, float b, float neg1, uint32_t& 
 // every VALU producer needs ONE wait state before the MFMA, overwriting a source right after it
 // is safe, with or without a sibling MFMA stream; tools/mfma_branch_hazard_probe.hip: a VALU read
 // of the result needs 12 states for the last accumulator register, 6 for the first, and hipcc
-// provides them).  Round 3 fenced these triples (every operand complete OETR_SPLIT3_PAD + 1
+// provides them).  Round 3 fenced these triples (every operand complete 8
 // states before the first MFMA, the three MFMAs back to back) when the split-f16 KV state
 // returned timing-dependent results; round 4 showed the fences were NOT what removed the
 // failures (the fenced two-path state still failed 7 of 37 000 at s_setprio 3; what every
 // failing build shares is a run-time branch between two forms of the state code, see
 // encoder.hip).  The attention apply - the only user left - has one code path and 0 differing
 // of 858 000 forwards with the fences; they stay as they were measured (0.3 us per launch).
-#ifndef OETR_SPLIT3_PAD
-#define OETR_SPLIT3_PAD 7
-#endif
-#define OETR_STR2(x) #x
-#define OETR_STR(x) OETR_STR2(x)
 template <bool FENCE = true>
 __device__ __forceinline__ void mma16_split3(const f32x4& ah, const f32x4& al, const f32x4& bh,
                                              const f32x4& bl, f32x16& main, f32x16& cross) {
   if constexpr (FENCE) {
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop " OETR_STR(OETR_SPLIT3_PAD));
+    asm volatile("s_nop 7");
     __builtin_amdgcn_sched_barrier(0);
   }
   cross = mma16<GM_SPLIT>(ah, bl, cross);
@@ -613,13 +571,8 @@ struct GemmRegsH {
 //            k = 16*ks + 8*(lane>>5) + {0..7}.
 //   GM_SPLIT: acc = main + cross/2^11 is formed at the end; `acc` enters as the initial
 //   main part.
-#ifndef OETR_SPLIT_DEPTH
-#define OETR_SPLIT_DEPTH 3   // register buffers in the weight/activation prefetch ring
-#endif
-#ifndef OETR_SPLIT_U1
-#define OETR_SPLIT_U1 2   // chunk depth (k16 steps) when a wave owns one n-tile (8-wave shape)
-#endif
-template <int M, int K, int NT, int U = (NT == 1 ? OETR_SPLIT_U1 : 4)>
+//   U: chunk depth in k16 steps (2 when a wave owns one n-tile - the 8-wave shape).
+template <int M, int K, int NT, int U = (NT == 1 ? 2 : 4)>
 __device__ __forceinline__ void gemm_rows32_h(const _Float16* __restrict__ Ahi,
                                               const _Float16* __restrict__ Alo, int lda,
                                               const f32x4* __restrict__ Whi,
@@ -676,7 +629,6 @@ __device__ __forceinline__ void gemm_rows32_h(const _Float16* __restrict__ Ahi,
     }
   };
 
-#if OETR_SPLIT_DEPTH == 3
   // ring of three register buffers: two chunks of fragments in flight while the
   // third is consumed (per-CU weight streaming is latency-bound: ~2000 cycles per
   // L2 round trip under the all-workgroups-read-the-same-lines load)
@@ -701,20 +653,6 @@ __device__ __forceinline__ void gemm_rows32_h(const _Float16* __restrict__ Ahi,
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-#else
-  GemmRegsH<M, NT, U> r0, r1;
-  fetch(r0, 0);
-  for (int c = 0; c < NCH; c += 2) {
-    fetch(r1, c + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(r0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (c + 2 < NCH) fetch(r0, c + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(r1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#endif
   if constexpr (TWO) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -841,22 +779,10 @@ __device__ __forceinline__ void ln_rows(const float* S, int tid, f32x4 (&xn)[F4]
 // Generic form (exact-f32 mode, or a wave owning several n-tiles): no run-
 // ahead, plain calls.
 // ---------------------------------------------------------------------------
-#ifndef OETR_WSTREAM
-#define OETR_WSTREAM 1
-#endif
 // Ring geometry (tools/variants A/B on MI355X, k_encoder<B,A> at 8 pairs @640x640, split
 // mode): chunks of 2 k16-steps, ring of 3: 46.1 us; ring of 4: 50.7 (registers); chunks
 // of ONE step, ring of 6 (5 steps = 10 KB per wave in flight): 42.3; ring of 8: 48.4.
 // The single-plane modes stream at ~47 B/clk/CU whatever the depth (L1-rate bound).
-#ifndef OETR_RING
-#define OETR_RING 6     // ring depth (chunks) of the two-plane (split) weight stream
-#endif
-#ifndef OETR_RING1
-#define OETR_RING1 6    // ring depth of the single-plane (f16 / bf16) weight stream
-#endif
-#ifndef OETR_WS_U
-#define OETR_WS_U 1     // k16 steps per chunk
-#endif
 template <int M, int NT, bool STREAMED = (gm_half(M) && NT == 1)>
 struct WStream {
   static constexpr int adv(int, int) { return 0; }
@@ -872,11 +798,10 @@ struct WStream {
   }
 };
 
-#if OETR_WSTREAM
 template <int M>
 struct WStream<M, 1, true> {
   static constexpr bool TWO = gm_planes(M) == 2;
-  static constexpr int U = OETR_WS_U, D = TWO ? OETR_RING : OETR_RING1, PRE = D - 1;
+  static constexpr int U = 1, D = 6, PRE = D - 1;   // k16 steps per chunk; ring depth in chunks, both plane counts
   struct BChunk { f32x4 bh[U], bl[TWO ? U : 1]; };
   struct AChunk { f32x4 ah[U], al[TWO ? U : 1]; };
   BChunk ring[D];
@@ -975,7 +900,6 @@ struct WStream<M, 1, true> {
     }
   }
 };
-#endif  // OETR_WSTREAM
 
 // ---- 64-token workgroup shape (k_encoder64, conv_p_body64) ----
 constexpr int RT = 64;                                   // token rows per workgroup
@@ -1014,15 +938,6 @@ struct PlanesT {  // 16-bit planes [ROWS_P][LDAH] (hi, and lo*2^11 in GM_SPLIT) 
 };
 typedef PlanesT<GM_SPLIT> Planes2;
 
-#ifndef OETR_RING2
-#define OETR_RING2 4   // k16 steps of B fragments in the ring (one being consumed), split mode
-#endif
-#ifndef OETR_RING2_1P
-#define OETR_RING2_1P 4   // the same for the single-plane modes
-#endif
-#ifndef OETR_RING2_32
-#define OETR_RING2_32 6   // ... and for the 32-row form of the body (NMT = 1)
-#endif
 struct NoEpi { template <class T> __device__ __forceinline__ void operator()(T) const {} };
 
 // ROWS: how many of the tile's two 32-row MFMA tiles run.  2 / 1: fixed at compile time - the
@@ -1039,9 +954,10 @@ struct NoEpi { template <class T> __device__ __forceinline__ void operator()(T) 
 template <int M, int ROWS = 0, int NMT = 2>
 struct WStream2T {
   static constexpr bool TWO = gm_planes(M) == 2;
+  // D: k16 steps of B fragments in the ring (one being consumed) - 4 with two row tiles in every mode, 6 with one
   // (one row tile: the GEMM phases are bound by the weight stream, which wants more fragments in flight -
   //  and the registers of the second row tile are free for them)
-  static constexpr int D = NMT == 1 ? OETR_RING2_32 : TWO ? OETR_RING2 : OETR_RING2_1P, PRE = D - 1, NS = C / 16;  // every GEMM here has K = 256: 16 steps
+  static constexpr int D = NMT == 1 ? 6 : 4, PRE = D - 1, NS = C / 16;  // every GEMM here has K = 256: 16 steps
   struct BStep { f32x4 bh, bl; };
   struct AStep { f32x4 ah[NMT], al[NMT]; };
   BStep ring[D];

@@ -718,9 +718,7 @@ __device__ __forceinline__ void decoder_body4(const DecLaunch& p, int img, int j
   PHASE_STAMP(p, 9);
 }
 
-#ifndef OETR_DEC_THREADS
-#define OETR_DEC_THREADS 512   // measured equal to 1024 (the chain is L1-rate bound)
-#endif
+constexpr int DEC_WG_THREADS = 512;   // measured equal to 1024 (the chain is L1-rate bound)
 template <int T>
 __global__ __launch_bounds__(T) void k_decoder(DecLaunch p) {
   __shared__ __attribute__((aligned(16))) float smem[DecSmem<T>::TOTAL];
@@ -735,7 +733,7 @@ hipError_t launch_decoder(const DecLaunch& p, hipStream_t s) {
   if (p.ksplit == DEC_K)
     hipLaunchKernelGGL(k_decoder4, dim3(2 * p.g.N * DEC_K), dim3(512), 0, s, p);
   else
-    hipLaunchKernelGGL(k_decoder<OETR_DEC_THREADS>, dim3(2 * p.g.N), dim3(OETR_DEC_THREADS), 0, s, p);
+    hipLaunchKernelGGL(k_decoder<DEC_WG_THREADS>, dim3(2 * p.g.N), dim3(DEC_WG_THREADS), 0, s, p);
   return hipGetLastError();
 }
 
@@ -749,9 +747,6 @@ __global__ __launch_bounds__(512) void k_decoder_convp(DecLaunch d, HeatLaunch h
   constexpr int LDS_FLOATS = DecSmem<512>::TOTAL > TILE ? DecSmem<512>::TOTAL : TILE;
   __shared__ __attribute__((aligned(16))) float smem[LDS_FLOATS];
   const int nd = 2 * d.g.N * d.ksplit;
-#ifdef OETR_ROLE_ABL   // timing experiments only: 1 = decoder workgroups only, 2 = conv-P only
-  if ((OETR_ROLE_ABL == 1) != ((int)blockIdx.x < nd)) return;
-#endif
   if ((int)blockIdx.x < nd) {
     if (d.ksplit == DEC_K) decoder_body4(d, blockIdx.x / DEC_K, blockIdx.x % DEC_K, smem);
     else decoder_body<512>(d, blockIdx.x, smem);

@@ -994,7 +994,7 @@ __device__ __forceinline__ void kv_state_write(const f32x16& kv, float ksum, int
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     f32x4 o = {kv[4 * q], kv[4 * q + 1], kv[4 * q + 2], kv[4 * q + 3]};
-    store16<(OETR_WT & 4) != 0>(reinterpret_cast<float*>(dst), (q * 64 + (unsigned)lane) * 16u, o);
+    store16(reinterpret_cast<float*>(dst), (q * 64 + (unsigned)lane) * 16u, o);
   }
   if (lane < 32) (ks_out + (size_t)slot * C + wave * HD)[(unsigned)lane] = ksum;
 }
@@ -1306,7 +1306,7 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
     for (int i = 0; i < RTW / 8; ++i) {
       const int r = wave + 8 * i;   // (scalar: a wave-uniform branch, an SGPR row address)
       if (r < nvalid)
-        store16<(OETR_WT & 1) != 0>(p.x + (row_base + r) * C, 16u * (unsigned)lane,
+        store16(p.x + (row_base + r) * C, 16u * (unsigned)lane,
                                     *reinterpret_cast<const f32x4*>(Xf + r * LDA + 4 * lane));
     }
     PHASE_STAMP(p, 8);
@@ -1402,7 +1402,7 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
           if constexpr (pr % 2 == 0) { qhi[0] = __builtin_bit_cast(uint32_t, a); qhi[1] = __builtin_bit_cast(uint32_t, b); }
           else {
             qhi[2] = __builtin_bit_cast(uint32_t, a); qhi[3] = __builtin_bit_cast(uint32_t, b);
-            store16<(OETR_WT & 2) != 0>(reinterpret_cast<float*>(qf), ((mt * 4 + pr / 2) * 64 + (unsigned)lane) * 16u,
+            store16(reinterpret_cast<float*>(qf), ((mt * 4 + pr / 2) * 64 + (unsigned)lane) * 16u,
                                         __builtin_bit_cast(f32x4, qhi));
           }
         } else {
@@ -1410,9 +1410,9 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
           cvt_planes2<GM_SPLIT>(a, b, h, l, rg);
           qhi[j] = h; qlo[j] = l;
           if constexpr (j == 3) {
-            store16<(OETR_WT & 2) != 0>(reinterpret_cast<float*>(qf), ((mt * 4 + 2 * s2) * 64 + (unsigned)lane) * 16u,
+            store16(reinterpret_cast<float*>(qf), ((mt * 4 + 2 * s2) * 64 + (unsigned)lane) * 16u,
                                         __builtin_bit_cast(f32x4, qhi));
-            store16<(OETR_WT & 2) != 0>(reinterpret_cast<float*>(qf), ((mt * 4 + 2 * s2 + 1) * 64 + (unsigned)lane) * 16u,
+            store16(reinterpret_cast<float*>(qf), ((mt * 4 + 2 * s2 + 1) * 64 + (unsigned)lane) * 16u,
                                         __builtin_bit_cast(f32x4, qlo));
           }
         }
@@ -1523,13 +1523,31 @@ __global__ __launch_bounds__(512) void k_encoder32m(EncLaunch p) {
   encoder64_body<HAS_B, TAIL, MODE, POL, 2, TM, MASKED>(p, smem);
 }
 
-#ifndef OETR_SPLIT_WAVES
-#define OETR_SPLIT_WAVES 8
-#endif
-#ifndef OETR_F32_WAVES
-#define OETR_F32_WAVES 4
-#endif
+// Run-time (has_b, tail) -> compile-time tags: launch(b, t) gets a std::bool_constant and a std::integral_constant.
+// With a B phase every tail exists (0: A of the next layer, 1: decoder prep, 2: none); without one the tails
+// 0 .. NOB_TAIL_MAX do - api.hip launches (no B, 0) only, the first launch of a forward - and any other is
+// hipErrorInvalidValue with nothing launched.  NOB_TAIL_MAX decides which kernels exist (the table).
+template <int NOB_TAIL_MAX, class F>
+static hipError_t launch_b_tail(bool has_b, int tail, F launch) {
+  constexpr std::integral_constant<int, 0> t0{};
+  constexpr std::integral_constant<int, 1> t1{};
+  constexpr std::integral_constant<int, 2> t2{};
+  if (has_b) {
+    if (tail == 0) launch(std::true_type{}, t0);
+    else if (tail == 1) launch(std::true_type{}, t1);
+    else launch(std::true_type{}, t2);
+  } else {
+    if (tail == 0) launch(std::false_type{}, t0);
+    else if constexpr (NOB_TAIL_MAX == 0) return hipErrorInvalidValue;
+    else if (tail == 1) launch(std::false_type{}, t1);
+    else if constexpr (NOB_TAIL_MAX == 1) return hipErrorInvalidValue;
+    else launch(std::false_type{}, t2);
+  }
+  return hipGetLastError();
+}
 
+// Which kernel runs: guards first, then one line per kernel (template arguments after MODE: see each kernel;
+// b() / t() are the tags' values).  DESIGN.md 3.2 lists every instantiation and the setting that selects it.
 template <int MODE>
 static hipError_t launch_encoder_mode(const EncLaunch& p, bool has_b, int tail, hipStream_t s) {
   const dim3 grid(p.g.ntiles);
@@ -1538,133 +1556,65 @@ static hipError_t launch_encoder_mode(const EncLaunch& p, bool has_b, int tail, 
     // precision policy), linear attention, both tile sizes
     if constexpr (MODE == GM_SPLIT) {
       if (!p.mask[0] || !p.mask[1] || (p.policy != 0 && p.policy != 1) || p.attn_full) return hipErrorInvalidValue;
-#define OETR_LAUNCHM(B, T)                                                                                    \
-  do {                                                                                                        \
-    if (p.policy == 1) {                                                                                      \
-      if (p.tile_rows == RT) hipLaunchKernelGGL((k_encoder64<B, T, MODE, 1, true>), grid, dim3(512), 0, s, p);  \
-      else hipLaunchKernelGGL((k_encoder32m<B, T, MODE, 1, true>), grid, dim3(512), 0, s, p);                   \
-    } else {                                                                                                  \
-      if (p.tile_rows == RT) hipLaunchKernelGGL((k_encoder64<B, T, MODE, 0, true>), grid, dim3(512), 0, s, p);  \
-      else hipLaunchKernelGGL((k_encoder32m<B, T, MODE, 0, true>), grid, dim3(512), 0, s, p);                   \
-    }                                                                                                         \
-  } while (0)
-      if (has_b) {
-        if (tail == 0) OETR_LAUNCHM(true, 0);
-        else if (tail == 1) OETR_LAUNCHM(true, 1);
-        else OETR_LAUNCHM(true, 2);
-      } else {
-        if (tail == 0) OETR_LAUNCHM(false, 0);
-        else return hipErrorInvalidValue;   // (no B phase + a tail = zero encoder layers: api.hip rejects enc_layers < 1 before any launch)
-      }
-#undef OETR_LAUNCHM
-      return hipGetLastError();
+      return launch_b_tail<0>(has_b, tail, [&](auto b, auto t) {
+        if (p.policy == 1) {
+          if (p.tile_rows == RT) hipLaunchKernelGGL((k_encoder64<b(), t(), MODE, 1, true>), grid, dim3(512), 0, s, p);
+          else hipLaunchKernelGGL((k_encoder32m<b(), t(), MODE, 1, true>), grid, dim3(512), 0, s, p);
+        } else {
+          if (p.tile_rows == RT) hipLaunchKernelGGL((k_encoder64<b(), t(), MODE, 0, true>), grid, dim3(512), 0, s, p);
+          else hipLaunchKernelGGL((k_encoder32m<b(), t(), MODE, 0, true>), grid, dim3(512), 0, s, p);
+        }
+      });
     } else if constexpr (MODE == GM_F32) {
       // exact fp32: round 1-3's 32-row kernel, 4 waves (the re-run route of a masked batch)
       if (!p.mask[0] || !p.mask[1] || p.policy != 0 || p.attn_full) return hipErrorInvalidValue;
-#define OETR_LAUNCHMF(B, T) \
-  hipLaunchKernelGGL((k_encoder<B, T, MODE, OETR_F32_WAVES, false, 0, true>), grid, dim3(64 * OETR_F32_WAVES), 0, s, p)
-      if (has_b) {
-        if (tail == 0) OETR_LAUNCHMF(true, 0);
-        else if (tail == 1) OETR_LAUNCHMF(true, 1);
-        else OETR_LAUNCHMF(true, 2);
-      } else {
-        if (tail == 0) OETR_LAUNCHMF(false, 0);
-        else return hipErrorInvalidValue;
-      }
-#undef OETR_LAUNCHMF
-      return hipGetLastError();
+      return launch_b_tail<0>(has_b, tail, [&](auto b, auto t) {
+        hipLaunchKernelGGL((k_encoder<b(), t(), MODE, 4, false, 0, true>), grid, dim3(64 * 4), 0, s, p);
+      });
     } else {
       return hipErrorInvalidValue;
     }
   }
   if constexpr (gm_half(MODE)) {
-    if (p.tile_rows == RT) {
-#define OETR_LAUNCH64(B, T) hipLaunchKernelGGL((k_encoder64<B, T, MODE>), grid, dim3(512), 0, s, p)
-      if constexpr (MODE == GM_SPLIT) {   // precision policies exist for the two-plane mode
-        if (p.policy == 1) {
-#define OETR_LAUNCH64P(B, T) hipLaunchKernelGGL((k_encoder64<B, T, MODE, 1>), grid, dim3(512), 0, s, p)
-          if (has_b) {
-            if (tail == 0) OETR_LAUNCH64P(true, 0);
-            else if (tail == 1) OETR_LAUNCH64P(true, 1);
-            else OETR_LAUNCH64P(true, 2);
-          } else {
-            if (tail == 0) OETR_LAUNCH64P(false, 0);
-            else if (tail == 1) OETR_LAUNCH64P(false, 1);
-            else return hipErrorInvalidValue;
-          }
-#undef OETR_LAUNCH64P
-          return hipGetLastError();
-        }
+    if (p.tile_rows == RT) {   // 64 token rows: every 16-bit-plane mode; precision policies exist for the two-plane mode
+      if constexpr (MODE == GM_SPLIT) {
+        if (p.policy == 1)
+          return launch_b_tail<1>(has_b, tail, [&](auto b, auto t) {
+            hipLaunchKernelGGL((k_encoder64<b(), t(), MODE, 1>), grid, dim3(512), 0, s, p);
+          });
       }
       if (p.policy != 0) return hipErrorInvalidValue;
-      if (has_b) {
-        if (tail == 0) OETR_LAUNCH64(true, 0);
-        else if (tail == 1) OETR_LAUNCH64(true, 1);
-        else OETR_LAUNCH64(true, 2);
-      } else {
-        if (tail == 0) OETR_LAUNCH64(false, 0);
-        else if (tail == 1) OETR_LAUNCH64(false, 1);
-        else return hipErrorInvalidValue;
-      }
-#undef OETR_LAUNCH64
-      return hipGetLastError();
+      return launch_b_tail<1>(has_b, tail, [&](auto b, auto t) {
+        hipLaunchKernelGGL((k_encoder64<b(), t(), MODE>), grid, dim3(512), 0, s, p);
+      });
     }
   }
   if constexpr (MODE == GM_SPLIT) {
     if (!p.attn_full) {   // 32 token rows, two-plane mode, linear attention: the 64-row kernel's body on one row tile
       if (p.policy != 0 && p.policy != 1) return hipErrorInvalidValue;
-#define OETR_LAUNCH32M(B, T)                                                                    \
-  do {                                                                                          \
-    if (p.policy == 1) hipLaunchKernelGGL((k_encoder32m<B, T, MODE, 1>), grid, dim3(512), 0, s, p); \
-    else hipLaunchKernelGGL((k_encoder32m<B, T, MODE, 0>), grid, dim3(512), 0, s, p);            \
-  } while (0)
-      if (has_b) {
-        if (tail == 0) OETR_LAUNCH32M(true, 0);
-        else if (tail == 1) OETR_LAUNCH32M(true, 1);
-        else OETR_LAUNCH32M(true, 2);
-      } else {
-        if (tail == 0) OETR_LAUNCH32M(false, 0);
-        else if (tail == 1) OETR_LAUNCH32M(false, 1);
-        else return hipErrorInvalidValue;
-      }
-#undef OETR_LAUNCH32M
-      return hipGetLastError();
+      return launch_b_tail<1>(has_b, tail, [&](auto b, auto t) {
+        if (p.policy == 1) hipLaunchKernelGGL((k_encoder32m<b(), t(), MODE, 1>), grid, dim3(512), 0, s, p);
+        else hipLaunchKernelGGL((k_encoder32m<b(), t(), MODE, 0>), grid, dim3(512), 0, s, p);
+      });
     }
   }
-  // round 1-3's 32-row kernel: exact fp32 (4 waves), the single-plane modes, attention = 'full'
-  constexpr int NW = gm_half(MODE) ? OETR_SPLIT_WAVES : OETR_F32_WAVES;
+  // round 1-3's 32-row kernel: exact fp32 (4 waves), the single-plane modes (8 waves), attention = 'full'
+  constexpr int NW = gm_half(MODE) ? 8 : 4;
   if (p.policy != 0) return hipErrorInvalidValue;   // (policies exist in the two-plane mode only: handled above)
   if (p.attn_full) {
     // (the exact-fp32 build runs 8 waves here too: one head per wave in the attention core)
-    if constexpr ((gm_f16_range(MODE) && NW == 8) || MODE == GM_F32) {
-#define OETR_LAUNCHF(B, T) hipLaunchKernelGGL((k_encoder<B, T, MODE, 8, true>), grid, dim3(64 * 8), 0, s, p)
-      if (has_b) {
-        if (tail == 0) OETR_LAUNCHF(true, 0);
-        else if (tail == 1) OETR_LAUNCHF(true, 1);
-        else OETR_LAUNCHF(true, 2);
-      } else {
-        if (tail == 0) OETR_LAUNCHF(false, 0);
-        else return hipErrorInvalidValue;
-      }
-#undef OETR_LAUNCHF
-      return hipGetLastError();
+    if constexpr (gm_f16_range(MODE) || MODE == GM_F32) {
+      return launch_b_tail<0>(has_b, tail, [&](auto b, auto t) {
+        hipLaunchKernelGGL((k_encoder<b(), t(), MODE, 8, true>), grid, dim3(64 * 8), 0, s, p);
+      });
     } else {
       return hipErrorInvalidValue;
     }
   }
   if constexpr (MODE != GM_SPLIT) {
-#define OETR_LAUNCH(B, T) hipLaunchKernelGGL((k_encoder<B, T, MODE, NW>), grid, dim3(64 * NW), 0, s, p)
-    if (has_b) {
-      if (tail == 0) OETR_LAUNCH(true, 0);
-      else if (tail == 1) OETR_LAUNCH(true, 1);
-      else OETR_LAUNCH(true, 2);
-    } else {
-      if (tail == 0) OETR_LAUNCH(false, 0);
-      else if (tail == 1) OETR_LAUNCH(false, 1);
-      else OETR_LAUNCH(false, 2);
-    }
-#undef OETR_LAUNCH
-    return hipGetLastError();
+    return launch_b_tail<2>(has_b, tail, [&](auto b, auto t) {
+      hipLaunchKernelGGL((k_encoder<b(), t(), MODE, NW>), grid, dim3(64 * NW), 0, s, p);
+    });
   }
   return hipErrorInvalidValue;
 }

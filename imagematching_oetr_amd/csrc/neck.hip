@@ -141,22 +141,6 @@ constexpr int NC_STAGES = NECK_PIX * 4;        // 16 pixels x 4 channel quarters
 static_assert(NC_ROWB % 16 == 0 && (NC_ROWB / 4) % 64 == 4, "conflict-free b128 row stride");
 
 struct ConvB { f32x4 h, l; };                  // one k16-step of B fragments (hi, lo)
-#ifndef NECK_SLICE_MAJOR
-#define NECK_SLICE_MAJOR 0   // work-item order: 0 = tile-major (X rows of a tile share an L2), 1 = slice-major
-#endif
-#ifndef NECK_RW_SLICE_MAJOR
-#define NECK_RW_SLICE_MAJOR 0   // the row-window kernel's work-item order (see k_neck_conv_rw)
-#endif
-#ifndef NECK_RING8
-#define NECK_RING8 0   // 8-deep weight ring in the one-wave-per-SIMD shape: measured slower (433 vs 414 us)
-#endif
-#ifndef NECK_SPREAD
-#define NECK_SPREAD 0   // 1: issue the next stage's gather passes between the k16 steps (measured slower: 460 vs 441 us)
-#endif
-#ifndef NECK_ABL
-#define NECK_ABL 0   // timing experiments only: 1 no A gathers, 2 no B loads, 4 no MFMA, 8 no LDS writes,
-                     // (row-window kernel) 16 no A re-reads from LDS, 32 no stage barrier
-#endif
 
 // RTW = 32-row MFMA tiles per wave: a workgroup covers MT = 64 * RTW output positions
 // (two row halves of RTW tiles each) - 256, 192 or 128.  Fewer rows per workgroup mean
@@ -183,12 +167,7 @@ __global__ __launch_bounds__(512) void k_neck_conv(NeckConvLaunch p) {
   // (Slice-major - a weight slice stays in L2, the tiles' X rows stream - measured equal:
   //  518.8 vs 525.6 us at 16 maps of 40x40; the kernel is not fabric-bound.)
   const int logical = xcd_remap(blockIdx.x, p.nblocks);
-#if NECK_SLICE_MAJOR
-  const int mtiles = p.nblocks / p.items_per_mt;
-  const int it = logical / mtiles, mt = logical - it * mtiles;
-#else
   const int mt = logical / p.items_per_mt, it = logical - mt * p.items_per_mt;
-#endif
   const int ci = it >= p.conv[2].item0 ? 2 : (it >= p.conv[1].item0 ? 1 : 0);
   const NeckConvDesc& cd = p.conv[ci];
   const int rem = it - cd.item0;
@@ -229,13 +208,11 @@ __global__ __launch_bounds__(512) void k_neck_conv(NeckConvLaunch p) {
     int2 info[RTW];
 #pragma unroll
     for (int j = 0; j < RTW; ++j) info[j] = rowinfo[(tid >> 4) + HALF_ROWS * jh + 32 * j];
-    if (NECK_ABL & 1) return;
 #pragma unroll
     for (int j = 0; j < RTW; ++j) sreg[j] = xplane[src_unit(info[j], ky, kx, cq)];
   };
   auto stage_write = [&](int buf, int jh) {
     char* dst = smem + buf * BUF + ((tid >> 4) + HALF_ROWS * jh) * NC_ROWB + slot * 16;
-    if (NECK_ABL & 8) return;
 #pragma unroll
     for (int j = 0; j < RTW; ++j) *reinterpret_cast<f32x4*>(dst + 32 * j * NC_ROWB) = sreg[j];
   };
@@ -273,23 +250,17 @@ __global__ __launch_bounds__(512) void k_neck_conv(NeckConvLaunch p) {
       const f16x8 bh = __builtin_bit_cast(f16x8, bf[kk].h), bl = __builtin_bit_cast(f16x8, bf[kk].l);
 #pragma unroll
       for (int tp = 0; tp < RTW; tp += 2) {
-        constexpr bool dummy = false; (void)dummy;
         const bool pair = tp + 1 < RTW;   // compile-time after unrolling
         const int t1 = pair ? tp + 1 : tp;
         const f16x8 a0h = __builtin_bit_cast(f16x8, ah[tp]), a0l = __builtin_bit_cast(f16x8, al[tp]);
         const f16x8 a1h = __builtin_bit_cast(f16x8, ah[t1]), a1l = __builtin_bit_cast(f16x8, al[t1]);
-        if (NECK_ABL & 4) {
-          acc[tp][0] += (float)a0h[0] + (float)a0l[0] + (float)bh[0] + (float)bl[0];
-          if (pair) acc[t1][0] += (float)a1h[0] + (float)a1l[0];
-        } else {
-          // (dependent MFMAs on one accumulator are kept two apart where a pair exists)
-          acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bh, acc[tp], 0, 0, 0);
-          if (pair) acc[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bh, acc[t1], 0, 0, 0);
-          cross[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bl, cross[tp], 0, 0, 0);
-          if (pair) cross[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bl, cross[t1], 0, 0, 0);
-          cross[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, bh, cross[tp], 0, 0, 0);
-          if (pair) cross[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, bh, cross[t1], 0, 0, 0);
-        }
+        // (dependent MFMAs on one accumulator are kept two apart where a pair exists)
+        acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bh, acc[tp], 0, 0, 0);
+        if (pair) acc[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bh, acc[t1], 0, 0, 0);
+        cross[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, bl, cross[tp], 0, 0, 0);
+        if (pair) cross[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bl, cross[t1], 0, 0, 0);
+        cross[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, bh, cross[tp], 0, 0, 0);
+        if (pair) cross[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, bh, cross[t1], 0, 0, 0);
         if (kk < 3) {  // these tiles' fragments for the next k16 step
 #pragma unroll
           for (int t = tp; t <= t1; ++t) {
@@ -299,7 +270,7 @@ __global__ __launch_bounds__(512) void k_neck_conv(NeckConvLaunch p) {
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (more && !(NECK_ABL & 2)) {  // the same k16 step of the next stage into the slot just consumed
+      if (more) {  // the same k16 step of the next stage into the slot just consumed
         bf[kk].h = wh[((s + 1) * 4 + kk) * 64 + ln];
         bf[kk].l = wl[((s + 1) * 4 + kk) * 64 + ln];
       }
@@ -374,12 +345,7 @@ __global__ __launch_bounds__(64 * NW) void k_neck_conv_rw(NeckConvLaunch p) {
   const int nt = wave & 3, rh = wave >> 2;
 
   const int logical = xcd_remap(blockIdx.x, p.nblocks);
-#if NECK_RW_SLICE_MAJOR
-  const int mtiles = p.nblocks / p.items_per_mt;
-  const int it = logical / mtiles, mt = logical - it * mtiles;
-#else
-  const int mt = logical / p.items_per_mt, it = logical - mt * p.items_per_mt;
-#endif
+  const int mt = logical / p.items_per_mt, it = logical - mt * p.items_per_mt;   // tile-major, as in k_neck_conv
   const int ci = it >= p.conv[2].item0 ? 2 : (it >= p.conv[1].item0 ? 1 : 0);
   const NeckConvDesc& cd = p.conv[ci];
   const int rem = it - cd.item0;
@@ -458,7 +424,6 @@ __global__ __launch_bounds__(64 * NW) void k_neck_conv_rw(NeckConvLaunch p) {
   }
   auto stage_write = [&](int buf) {
     char* dst = smem + buf * BUF;
-    if (NECK_ABL & 8) return;
 #pragma unroll
     for (int q = 0; q < NPASS; ++q) *reinterpret_cast<f32x4*>(dst + woff[q]) = sreg[q];
   };
@@ -476,8 +441,8 @@ __global__ __launch_bounds__(64 * NW) void k_neck_conv_rw(NeckConvLaunch p) {
   auto stages = [&](auto gr_tag) {
     constexpr int GR = decltype(gr_tag)::value, KSTEPS = 4 * GR;
     // weight ring: RING k16 steps in flight (a divisor of KSTEPS, so slots are static);
-    // the one-wave-per-SIMD shape has the registers - and no second wave - for 8
-    constexpr int RING = (NW == 4 && GR >= 2 && NECK_RING8) ? 8 : 4;
+    // (8 in the one-wave-per-SIMD shape, which has the registers for it: measured slower, 433 vs 414 us)
+    constexpr int RING = 4;
     ConvB bf[RING];
 #pragma unroll
     for (int kk = 0; kk < RING; ++kk) { bf[kk].h = wh[kk * 64 + ln]; bf[kk].l = wl[kk * 64 + ln]; }
@@ -485,8 +450,8 @@ __global__ __launch_bounds__(64 * NW) void k_neck_conv_rw(NeckConvLaunch p) {
     for (int s = 0; s < nstg; ++s) {
       const int cur = s & 1;
       const char* abase = smem + cur * BUF;
-      // the next stage's gathers go out after the first k16 step (NECK_SPREAD: one pass at
-      // a time between the steps instead - slower); the last stage re-stages itself: unused
+      // the next stage's gathers go out after the first k16 step (one pass at a time between
+      // the steps instead: measured slower, 460 vs 441 us); the last stage re-stages itself: unused
       const int sn = min(s + 1, nstg - 1), cqn = (sn & 7) * 128;
       if ((sn & 7) == 0) stage_addr(sn);
       f32x4 ah[RTW], al[RTW];
@@ -498,7 +463,6 @@ __global__ __launch_bounds__(64 * NW) void k_neck_conv_rw(NeckConvLaunch p) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int st = 0; st < KSTEPS; ++st) {         // tap st >> 1, 16-channel step st & 1
-        constexpr int dummy = 0; (void)dummy;
         const int kk = st & (RING - 1);
         const f16x8 bh = __builtin_bit_cast(f16x8, bf[kk].h), bl = __builtin_bit_cast(f16x8, bf[kk].l);
         const int nxt = ((st + 1) >> 1) * RW_ENT + ((st + 1) & 1) * 32;   // the k16 step after this one
@@ -514,7 +478,7 @@ __global__ __launch_bounds__(64 * NW) void k_neck_conv_rw(NeckConvLaunch p) {
           if (pair) cross[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bl, cross[t1], 0, 0, 0);
           cross[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, bh, cross[tp], 0, 0, 0);
           if (pair) cross[t1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, bh, cross[t1], 0, 0, 0);
-          if (st + 1 < KSTEPS && !(NECK_ABL & 16)) {
+          if (st + 1 < KSTEPS) {
 #pragma unroll
             for (int t = tp; t <= t1; ++t) {
               ah[t] = *reinterpret_cast<const f32x4*>(abase + aoff[t] + nxt);
@@ -523,21 +487,18 @@ __global__ __launch_bounds__(64 * NW) void k_neck_conv_rw(NeckConvLaunch p) {
           }
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (!(NECK_ABL & 1)) {                      // gather passes of the next stage due at this step
+        if (st == 0) {                              // the gather passes of the next stage
 #pragma unroll
-          for (int q = 0; q < NPASS; ++q)
-            if (NECK_SPREAD ? q * (KSTEPS - 4 > 0 ? KSTEPS - 4 : 1) / NPASS == st : st == 0) sreg[q] = *reinterpret_cast<const f32x4*>(xplane + src[q] + cqn);
+          for (int q = 0; q < NPASS; ++q) sreg[q] = *reinterpret_cast<const f32x4*>(xplane + src[q] + cqn);
         }
         const int gi = min(gstep, NC_STAGES * 4 - 1);   // refill the ring slot just consumed
-        if (!(NECK_ABL & 2)) {
-          bf[kk].h = wh[(size_t)gi * 64 + ln];
-          bf[kk].l = wl[(size_t)gi * 64 + ln];
-        }
+        bf[kk].h = wh[(size_t)gi * 64 + ln];
+        bf[kk].l = wl[(size_t)gi * 64 + ln];
         ++gstep;
         __builtin_amdgcn_sched_barrier(0);
       }
       stage_write(cur ^ 1);
-      if (!(NECK_ABL & 32)) __syncthreads();
+      __syncthreads();
     }
   };
   if (groups == 4) stages(std::integral_constant<int, 4>{});

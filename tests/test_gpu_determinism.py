@@ -2,7 +2,7 @@
 whatever ran before them.
 
 Regression test for the timing-dependent linear-attention states of round 3 (DESIGN 3.2,
-csrc/encoder.hip: OETR_SPLIT_STATE, csrc/common.h: mma16_split3 / OETR_VMCNT_LOADS).  What
+csrc/encoder.hip: OETR_SPLIT_STATE, csrc/common.h: mma16_split3 and the OETR_SOAK_AMP amplifiers).  What
 exposed them - and what this test therefore does - is INTERLEAVING shapes: a big batch between
 two forwards of a small one leaves the weights cold in L2, the waves of a workgroup drift apart
 behind their weight loads, and the ragged last tile of an image (a workgroup with short GEMM

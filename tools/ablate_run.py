@@ -1,11 +1,11 @@
 """Timing attribution on the GPU with the -DOETR_ABLATE library
-(tools/ablate.sh).  Results are WRONG numerically by construction; only the
+(tools/variants.sh ablate -DOETR_ABLATE).  Results are WRONG numerically by construction; only the
 per-kernel durations matter."""
 import os, sys, json
 from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
-os.environ['OETR_HIP_LIB'] = str(REPO / 'tools' / 'ablate' / 'liboetr_hip.so')
+os.environ['OETR_HIP_LIB'] = str(REPO / 'tools' / 'variants' / 'ablate' / 'liboetr_hip.so')
 import torch
 import imagematching_oetr_amd as pkg
 

@@ -1,14 +1,14 @@
 #!/bin/bash
 # Register / LDS / scratch figures of every kernel in the shipped sources, one line per kernel:
 #   tools/kernel_resources.sh > profiles/<round>_kernel_resources.txt
-# (hipcc's -Rpass-analysis=kernel-resource-usage remarks, same flags as csrc/Makefile; no GPU needed)
+# (hipcc's -Rpass-analysis=kernel-resource-usage remarks on csrc/Makefile's `asm` target: its sources, its flags
+#  per file; no GPU needed)
 set -e
-cd "$(dirname "$0")/../imagematching_oetr_amd/csrc"
-echo "# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage of the shipped sources ($(git log -1 --format=%h 2>/dev/null || echo tree)), one line per kernel"
+CSRC="$(cd "$(dirname "$0")/../imagematching_oetr_amd/csrc" && pwd)"
+TMP=$(mktemp -d); trap 'rm -rf "$TMP"' EXIT
+echo "# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage of the shipped sources ($(git -C "$CSRC" log -1 --format=%h 2>/dev/null || echo tree)), one line per kernel"
 echo "# VGPRs | AGPRs | scratch B/lane | VGPR spills | SGPR spills | LDS B/block | waves/SIMD | kernel"
-for f in encoder decoder heads attention neck crop reader; do
-  extra=""; case $f in encoder|attention) extra="-fno-slp-vectorize";; esac      # (per-file flags of csrc/Makefile)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $extra -Rpass-analysis=kernel-resource-usage -c $f.hip -o /dev/null 2>&1 |
+make -s -C "$TMP" -f "$CSRC/Makefile" VPATH="$CSRC" RESOURCES=1 asm 2>&1 |
     python3 -c '
 import re, sys
 cur = {}
@@ -23,4 +23,3 @@ for line in sys.stdin:
     if k == "LDS Size [bytes/block]":
         print("%4s | %3s | %4s | %3s | %3s | %7s | %2s | %s" % (cur.get("VGPRs"), cur.get("AGPRs"), cur.get("ScratchSize [bytes/lane]"), cur.get("VGPRs Spill"), cur.get("SGPRs Spill"), cur.get("LDS Size [bytes/block]"), cur.get("Occupancy [waves/SIMD]"), cur["name"]))
 '
-done

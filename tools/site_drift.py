@@ -1,7 +1,7 @@
 """Per-GEMM-site precision study on the CPU ORACLE (fp64): round the operands of one site (or a
 combination) to f16 / bf16 inside the oracle's graph and record the drift of memory / hs / cxy /
 tlbr and the worst 1 - IoU of the boxes against the unrounded run, on the seeded golden cases.
-Predicts the GPU table (tools/site_variants.sh -> profiles/r3_site_drift.jsonl) to two digits;
+Predicts the GPU table (profiles/r3_site_drift.jsonl, measured with one-site variant builds) to two digits;
 DESIGN.md 3.10.  Test infrastructure only (imports oracle/).
     python tools/site_drift.py [out.json]
 """
