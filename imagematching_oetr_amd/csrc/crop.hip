@@ -23,8 +23,12 @@
 // centres (d + 0.5) * scale - 0.5, taps clamped to the border, horizontal then
 // vertical); cv2 is not available in the build image: resize numerics are
 // parity-unpinned (oracle/crop_oracle.py restates the same published algorithm).
+//
+// The arithmetic itself (geometry, cubic weights, source coordinate, tap sum) lives in crop_sample.h,
+// shared with the batched entry (crop_batch.hip).
 #include "../../include/oetr_hip.h"
 #include "common.h"
+#include "crop_sample.h"
 
 namespace oetr {
 
@@ -44,82 +48,8 @@ struct CropLaunch {
 __global__ void k_crop_geometry(CropLaunch p) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   oetr_crop_info g;
-  int bw[2], bh[2];
-  for (int i = 0; i < 2; ++i) {
-    for (int j = 0; j < 4; ++j) {
-      // bbox * overlap_scales in float32 (torch tensor product), then .int() truncation
-      const float v = p.box[i][j] * p.scale[i][j & 1];
-      g.sbox[i][j] = v;
-      g.box[i][j] = (int)v;
-    }
-    bw[i] = g.box[i][2] - g.box[i][0];
-    bh[i] = g.box[i][3] - g.box[i][1];
-  }
-  int mn = min(min(bw[0], bh[0]), min(bw[1], bh[1]));
-  bool valid = mn > 1;
-  if (valid && p.gate_mode == 1) {   // 'pragueparks-val': integer floor_divide scores
-    const int score = max(max(bw[0] / bw[1], bh[0] / bh[1]), max(bw[1] / bw[0], bh[1] / bh[0]));
-    valid = score > 2;
-  }
-  // the larger-area image provides the target size (utils.py:525-534)
-  const long a0 = (long)p.w[0] * p.h[0], a1 = (long)p.w[1] * p.h[1];
-  const int ow = a0 >= a1 ? p.w[0] : p.w[1], oh = a0 >= a1 ? p.h[0] : p.h[1];
-  for (int i = 0; i < 2; ++i) {
-    if (!valid) {
-      g.box[i][0] = 0; g.box[i][1] = 0; g.box[i][2] = p.w[i]; g.box[i][3] = p.h[i];
-      g.sbox[i][0] = 0.f; g.sbox[i][1] = 0.f; g.sbox[i][2] = (float)p.w[i]; g.sbox[i][3] = (float)p.h[i];
-      g.crop_w[i] = g.new_w[i] = g.out_w[i] = p.w[i];
-      g.crop_h[i] = g.new_h[i] = g.out_h[i] = p.h[i];
-      g.ratio[i][0] = g.ratio[i][1] = 1.0;
-      continue;
-    }
-    // python slicing image[:, y1:y2, x1:x2] clamps at the border
-    const int x1 = min(g.box[i][0], p.w[i]), x2 = min(g.box[i][2], p.w[i]);
-    const int y1 = min(g.box[i][1], p.h[i]), y2 = min(g.box[i][3], p.h[i]);
-    const int cw = max(0, x2 - x1), ch = max(0, y2 - y1);
-    g.crop_w[i] = cw; g.crop_h[i] = ch;
-    double rx, ry, nw, nh;
-    if (p.keep_aspect) {   // patch_resize, extractor != 'disk'
-      if ((double)ow / (double)cw > (double)oh / (double)ch) {
-        rx = (double)oh / (double)ch; nw = rx * (double)cw; nh = (double)oh;
-      } else {
-        rx = (double)ow / (double)cw; nw = (double)ow; nh = rx * (double)ch;
-      }
-      ry = rx;
-    } else {
-      rx = (double)ow / (double)cw; ry = (double)oh / (double)ch; nw = (double)ow; nh = (double)oh;
-    }
-    g.ratio[i][0] = rx; g.ratio[i][1] = ry;
-    g.new_w[i] = (int)nw; g.new_h[i] = (int)nh;
-    g.out_w[i] = g.new_w[i]; g.out_h[i] = g.new_h[i];
-    if (p.size_divisor > 1) {   // math.ceil(new / d) * d in double
-      g.out_w[i] = (int)ceil((double)g.new_w[i] / p.size_divisor) * p.size_divisor;
-      g.out_h[i] = (int)ceil((double)g.new_h[i] / p.size_divisor) * p.size_divisor;
-    }
-  }
-  // A crop that does not fit the caller's capacity, or a degenerate one (the reference would
-  // raise from cv2.resize there), cannot be produced: valid = -1, sizes zeroed - NOT the same
-  // thing as a failed gate (valid = 0: the images pass through untouched).
-  bool fits = true;
-  for (int i = 0; i < 2; ++i)
-    if (g.out_w[i] > p.cap_w || g.out_h[i] > p.cap_h || g.new_w[i] > p.cap_w || g.new_h[i] > p.cap_h ||
-        g.new_w[i] <= 0 || g.new_h[i] <= 0)
-      fits = false;
-  if (!fits)
-    for (int i = 0; i < 2; ++i) g.out_w[i] = g.out_h[i] = g.new_w[i] = g.new_h[i] = 0;
-  g.valid = !fits ? -1 : (valid ? 1 : 0);
+  crop_geometry(p, g);   // crop_sample.h
   *p.info = g;
-}
-
-// OpenCV interpolateCubic (imgproc/resize.cpp), float32
-__device__ __forceinline__ void cubic_weights(float t, float (&w)[4]) {
-#pragma clang fp contract(off)   // separate multiplies and adds, like the C++ it restates
-  const float a = -0.75f;
-  w[0] = ((a * (t + 1.f) - 5.f * a) * (t + 1.f) + 8.f * a) * (t + 1.f) - 4.f * a;
-  w[1] = ((a + 2.f) * t - (a + 3.f)) * t * t + 1.f;
-  const float u = 1.f - t;
-  w[2] = ((a + 2.f) * u - (a + 3.f)) * u * u + 1.f;
-  w[3] = 1.f - w[0] - w[1] - w[2];
 }
 
 // One bicubic pass for both images (blockIdx.y = image, blockIdx.z = channel).
@@ -160,26 +90,14 @@ __global__ __launch_bounds__(256) void k_crop_resize(CropLaunch p) {
   if (idx >= (long)dw * dh || sw <= 0 || sh <= 0) return;
   const int dy = (int)(idx / dw), dx = (int)(idx - (long)dy * dw);
   // fx = (float)((dx + 0.5) * scale_x - 0.5) with scale in double, as OpenCV computes it
-  const float fx = (float)(((double)dx + 0.5) * ((double)sw / (double)dw) - 0.5);
-  const float fy = (float)(((double)dy + 0.5) * ((double)sh / (double)dh) - 0.5);
+  const float fx = crop_src_coord(dx, (double)sw / (double)dw);
+  const float fy = crop_src_coord(dy, (double)sh / (double)dh);
   const int sx = (int)floorf(fx), sy = (int)floorf(fy);
   float wx[4], wy[4];
   cubic_weights(fx - (float)sx, wx);
   cubic_weights(fy - (float)sy, wy);
   const float in_scale = PASS == 1 ? 255.0f : 1.0f;
-  float acc = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int yy = min(max(sy - 1 + j, 0), sh - 1);
-    const float* row = src + (size_t)(y0 + yy) * spitch + x0;
-    float r = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int xx = min(max(sx - 1 + i, 0), sw - 1);
-      r = __fadd_rn(r, __fmul_rn(row[xx] * in_scale, wx[i]));   // hresize: S[..]*a0 + ... left to right
-    }
-    acc = __fadd_rn(acc, __fmul_rn(r, wy[j]));                  // vresize: S0*b0 + S1*b1 + ...
-  }
+  const float acc = crop_tap_sum(src, spitch, x0, y0, sw, sh, sx, sy, wx, wy, in_scale);
   dst[idx] = PASS == 1 ? acc : acc / 255.0f;
 }
 

@@ -60,6 +60,12 @@ class _NeckWeights(C.Structure):
         ('input_proj2_w', _f32p), ('input_proj2_b', _f32p)]
 
 
+class _CropPair(C.Structure):
+    """``oetr_crop_pair`` (include/oetr_crop_batch.h): one row of a batched crop call's pair table."""
+    _fields_ = [('image', C.c_void_p * 2), ('h', C.c_int32 * 2), ('w', C.c_int32 * 2),
+                ('scale', (C.c_float * 2) * 2)]
+
+
 class _CropInfo(C.Structure):
     _fields_ = [('valid', C.c_int32), ('box', (C.c_int32 * 4) * 2),
                 ('crop_w', C.c_int32 * 2), ('crop_h', C.c_int32 * 2),
@@ -107,6 +113,10 @@ FLAG_INDEX = 4       # OETR_FLAG_INDEX: a pair index was outside its bank (a cal
 COVIS_ABI_VERSION = 1
 COVIS_EXPORTS = ('oetr_covis_abi_version', 'oetr_covis_workspace_bytes', 'oetr_covis_boxes')
 COVIS_PARAM_DOUBLES = 40   # OETR_COVIS_PARAM_DOUBLES
+
+# The batched crop extension (include/oetr_crop_batch.h): likewise
+CROP_BATCH_ABI_VERSION = 1
+CROP_BATCH_EXPORTS = ('oetr_crop_batch_abi_version', 'oetr_crop_batch_capacity', 'oetr_overlap_crop_batch')
 
 
 def hot_path_keys():
@@ -304,6 +314,16 @@ def load_library(path=None):
     lib.oetr_covis_boxes.argtypes = [vp, vp, vp, i, i, i, vp, sz] + [vp] * 7
     if lib.oetr_covis_abi_version() != COVIS_ABI_VERSION:
         raise RuntimeError(f'{p}: covis ABI version {lib.oetr_covis_abi_version()} != {COVIS_ABI_VERSION}')
+    # include/oetr_crop_batch.h
+    lib.oetr_crop_batch_abi_version.restype = i
+    lib.oetr_crop_batch_abi_version.argtypes = []
+    lib.oetr_crop_batch_capacity.restype = sz
+    lib.oetr_crop_batch_capacity.argtypes = [i, i, i, i, C.POINTER(i), C.POINTER(i)]
+    lib.oetr_overlap_crop_batch.restype = i
+    # pairs, n, channels, max_h, max_w, box1, box2, keep_aspect, size_divisor, gate_mode, tmp, out, capacity, info, stream
+    lib.oetr_overlap_crop_batch.argtypes = [vp, i, i, i, i, vp, vp, i, i, i, vp, vp, sz, vp, vp]
+    if lib.oetr_crop_batch_abi_version() != CROP_BATCH_ABI_VERSION:
+        raise RuntimeError(f'{p}: crop-batch ABI version {lib.oetr_crop_batch_abi_version()} != {CROP_BATCH_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib

@@ -175,7 +175,8 @@ def forward_pairs_raw(model, raw_pairs, resize=(640,), grayscale=True, align='di
     ``overlap_scales0/1`` (lists of float pairs), ``inp0`` / ``inp1`` (lists of
     ``[1,1|3,h,w]`` device tensors: the matcher's images) - exactly what
     ``overlap_crop(inp0[i], inp1[i], box0[i], box1[i], overlap_scales0[i], overlap_scales1[i])``
-    takes, with no host round trip in between."""
+    takes, with no host round trip in between.  :func:`crop_pairs` crops the whole result, one device
+    call per chunk of pairs."""
     from .reader import read_overlap_images
     device = _model_device(model)
     n = len(raw_pairs)
@@ -215,6 +216,28 @@ def forward_pairs_raw(model, raw_pairs, resize=(640,), grayscale=True, align='di
         di = torch.as_tensor(dst, device=res['box0'].device)
         res['box0'][di], res['box1'][di] = b0[rows], b1[rows]
     return res
+
+
+@torch.no_grad()
+def crop_pairs(res, keep_aspect=True, size_divisor=1, pragueparks=False, max_batch=8):
+    """The box -> crop step over :func:`forward_pairs_raw`'s result ``res``: ONE device call
+    (``crop_batch.overlap_crop_batch``) per chunk of ``max_batch`` consecutive pairs instead of one
+    ``overlap_crop`` per pair.  Returns a list of ``OverlapCropBatch``: pair ``i`` is entry
+    ``i % max_batch`` of chunk ``i // max_batch``, and equals ``overlap_crop`` on that pair alone.
+    ``res['inp0']`` / ``res['inp1']`` must be contiguous tensors, as the reader makes them: the pair table
+    holds their addresses (``crop_pair_table`` raises on a non-contiguous image, where ``overlap_crop``
+    would copy it)."""
+    from .crop_batch import crop_pair_table, overlap_crop_batch
+    if max_batch < 1:
+        raise ValueError('max_batch must be >= 1')
+    n = len(res['inp0'])
+    box0, box1 = res['box0'].contiguous(), res['box1'].contiguous()
+    chunks = []
+    for s in range(0, n, max_batch):
+        e = min(n, s + max_batch)
+        table = crop_pair_table(res['inp0'][s:e], res['inp1'][s:e], res['overlap_scales0'][s:e], res['overlap_scales1'][s:e])
+        chunks.append(overlap_crop_batch(table, box0[s:e], box1[s:e], keep_aspect, size_divisor, pragueparks))
+    return chunks
 
 
 @torch.no_grad()
