@@ -12,9 +12,16 @@
 // of integer atomicMax / atomicAdd per workgroup that saw an inlier: integer atomics commute, the result does not
 // depend on arrival order.  k_covis_finish (one thread per pair) decodes the accumulators into float32 boxes, the
 // valid byte and the count.  Masks are plain byte stores of 1 into memory the call cleared.
+//
+// The set entry (include/oetr_covis_set.h) runs the SAME per-pixel code - covis_block, the one copy - from
+// k_covis_warp_indexed: the two maps of a pair come from a device table by index and have sizes of their own, all
+// of it wave-uniform loads before the first pixel is touched; a pair the table does not vouch for is left alone.
+// k_covis_select is the reference's mining criterion (scale_diff > threshold) as an ordered compaction by ONE
+// workgroup, so the kept list is in list order whatever the scheduling.
+#include <cmath>
 #include <string>
 
-#include "../../include/oetr_covis.h"
+#include "../../include/oetr_covis_set.h"
 #include "common.h"
 
 namespace oetr {
@@ -26,19 +33,16 @@ constexpr int COVIS_ACC = 16;                                    // int32 per pa
 constexpr int SIDE = OETR_COVIS_MAX_SIDE;
 enum { A_MINU, A_MINV, A_MAXU, A_MAXV, A_MINI, A_MINJ, A_MAXI, A_MAXJ, A_COUNT, A_USED };
 
-// grid: x = blocks of COVIS_PIX pixels of one map, y = pair
-__global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __restrict__ depth1,
-                                                              const float* __restrict__ depth2,
-                                                              const double* __restrict__ params, int H, int W,
-                                                              int* __restrict__ acc, uint8_t* __restrict__ mask1,
-                                                              uint8_t* __restrict__ mask2) {
+// One workgroup's COVIS_PIX source pixels of one pair, from `block` * COVIS_PIX on: map 1 is d1 [H1][W1], map 2 is
+// d2 [H2][W2], P the pair's parameter block, acc its accumulators, m1 / m2 its masks (both nullptr: none).  Every
+// argument is wave-uniform.  The one copy of the per-pixel arithmetic: both entries run it.
+__device__ __forceinline__ void covis_block(const float* __restrict__ d1, int H1, int W1,
+                                            const float* __restrict__ d2, int H2, int W2,
+                                            const double* __restrict__ P, int block, int* __restrict__ acc,
+                                            uint8_t* __restrict__ m1, uint8_t* __restrict__ m2) {
 #pragma clang fp contract(off)
-  const int pair = blockIdx.y;
-  const int n_pix = H * W;                                        // <= 2^26
-  const size_t map = (size_t)pair * (size_t)n_pix;
-  const float* d1 = depth1 + map;
-  const float* d2 = depth2 + map;
-  const int first = (int)blockIdx.x * COVIS_PIX + (int)threadIdx.x;
+  const int n_pix = H1 * W1;                                      // <= 2^26
+  const int first = block * COVIS_PIX + (int)threadIdx.x;
 
   float z[COVIS_PER_THREAD];
 #pragma unroll
@@ -47,7 +51,6 @@ __global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __res
     z[k] = idx < n_pix ? d1[idx] : 0.0f;
   }
 
-  const double* P = params + (size_t)pair * OETR_COVIS_PARAM_DOUBLES;   // wave-uniform
   const double fx = P[16], fy = P[17], cx = P[18], cy = P[19];
   const double b1r = P[29], b1c = P[30], r1r = P[31], r1c = P[32];
   const double b2r = P[33], b2c = P[34], r2r = P[35], r2c = P[36];
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __res
   for (int k = 0; k < COVIS_PER_THREAD; ++k) {
     if (!(z[k] > 0.0f)) continue;                                 // no depth (0, negative, NaN) or past the map
     const int idx = first + k * COVIS_THREADS;
-    const int v = idx / W, u = idx - v * W;
+    const int v = idx / W1, u = idx - v * W1;
     const double Z = (double)z[k];
     const double x = ((double)u + b1c + 0.5) / r1c;
     const double y = ((double)v + b1r + 0.5) / r1r;
@@ -78,10 +81,10 @@ __global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __res
     for (int r = 0; r < 3; ++r) h[r] = (P[20 + 3 * r] * Xc + P[21 + 3 * r] * Yc) + P[22 + 3 * r] * Zc;
     const double u2 = (h[0] / h[2]) * r2c - b2c - 0.5;
     const double v2 = (h[1] / h[2]) * r2r - b2r - 0.5;
-    // trunc(u2) in [0, W) <=> -1 < u2 < W (false for NaN; +-inf and anything beyond int are outside)
-    if (!(u2 > -1.0 && u2 < (double)W && v2 > -1.0 && v2 < (double)H)) continue;
-    const int i = (int)u2, j = (int)v2;                           // towards zero; 0 <= i < W, 0 <= j < H
-    const double Z2 = (double)d2[(size_t)j * W + i];
+    // trunc(u2) in [0, W2) <=> -1 < u2 < W2 (false for NaN; +-inf and anything beyond int are outside)
+    if (!(u2 > -1.0 && u2 < (double)W2 && v2 > -1.0 && v2 < (double)H2)) continue;
+    const int i = (int)u2, j = (int)v2;                           // towards zero; 0 <= i < W2, 0 <= j < H2
+    const double Z2 = (double)d2[(size_t)j * W2 + i];
     if (!(fabs(Zc - Z2) < 0.5)) continue;
     best[A_MINU] = max(best[A_MINU], SIDE - u);
     best[A_MINV] = max(best[A_MINV], SIDE - v);
@@ -92,9 +95,9 @@ __global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __res
     best[A_MAXI] = max(best[A_MAXI], i + 1);
     best[A_MAXJ] = max(best[A_MAXJ], j + 1);
     best[A_COUNT] += 1;
-    if (mask1) {
-      mask1[map + (size_t)idx] = 1;
-      mask2[map + (size_t)j * W + i] = 1;
+    if (m1) {
+      m1[(size_t)idx] = 1;
+      m2[(size_t)j * W2 + i] = 1;
     }
   }
 
@@ -124,19 +127,62 @@ __global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __res
       n += part[w][A_COUNT];
     }
     if (n > 0) {
-      int* dst = acc + (size_t)pair * COVIS_ACC + a;
+      int* dst = acc + a;
       if (a == A_COUNT) atomicAdd(dst, r); else atomicMax(dst, r);
     }
   }
 }
 
-// one thread per pair
-__global__ void k_covis_finish(const int* __restrict__ acc, int n_pairs, float* __restrict__ box1,
-                               float* __restrict__ box2, uint8_t* __restrict__ valid, int32_t* __restrict__ count) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n_pairs) return;
+// grid: x = blocks of COVIS_PIX pixels of one map, y = pair
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __restrict__ depth1,
+                                                              const float* __restrict__ depth2,
+                                                              const double* __restrict__ params, int H, int W,
+                                                              int* __restrict__ acc, uint8_t* __restrict__ mask1,
+                                                              uint8_t* __restrict__ mask2) {
+  const int pair = blockIdx.y;
+  const size_t map = (size_t)pair * (size_t)(H * W);
+  covis_block(depth1 + map, H, W, depth2 + map, H, W, params + (size_t)pair * OETR_COVIS_PARAM_DOUBLES,
+              (int)blockIdx.x, acc + (size_t)pair * COVIS_ACC, mask1 ? mask1 + map : nullptr,
+              mask2 ? mask2 + map : nullptr);
+}
+
+// A table row the call may dereference: a pointer, sides within 1..SIDE, no more pixels than the caller vouched for.
+__device__ __forceinline__ bool covis_map_usable(const oetr_covis_map& m, int max_pixels) {
+  return m.depth != nullptr && m.H >= 1 && m.H <= SIDE && m.W >= 1 && m.W <= SIDE && m.H * m.W <= max_pixels;
+}
+
+// Both rows of pair `pair`, or false when the pair must not be dereferenced (include/oetr_covis_set.h).
+__device__ __forceinline__ bool covis_pair_maps(const oetr_covis_map* __restrict__ maps, int n_maps,
+                                                const int32_t* __restrict__ idx1, const int32_t* __restrict__ idx2,
+                                                int pair, int max_pixels, oetr_covis_map& a, oetr_covis_map& b) {
+  const int i1 = idx1[pair], i2 = idx2[pair];
+  if (i1 < 0 || i1 >= n_maps || i2 < 0 || i2 >= n_maps) return false;
+  a = maps[i1];
+  b = maps[i2];
+  return covis_map_usable(a, max_pixels) && covis_map_usable(b, max_pixels);
+}
+
+// grid: x = blocks of COVIS_PIX pixels up to max_pixels, y = pair.  The indices and the two table rows are
+// wave-uniform (scalar) loads; a block past its pair's own H1 * W1 leaves right after them.
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp_indexed(const oetr_covis_map* __restrict__ maps,
+                                                                      int n_maps, const int32_t* __restrict__ idx1,
+                                                                      const int32_t* __restrict__ idx2,
+                                                                      const double* __restrict__ params,
+                                                                      int max_pixels, int* __restrict__ acc) {
+  const int pair = blockIdx.y;
+  oetr_covis_map a, b;
+  if (!covis_pair_maps(maps, n_maps, idx1, idx2, pair, max_pixels, a, b)) return;
+  if ((int)blockIdx.x * COVIS_PIX >= a.H * a.W) return;
+  covis_block(a.depth, a.H, a.W, b.depth, b.H, b.W, params + (size_t)pair * OETR_COVIS_PARAM_DOUBLES,
+              (int)blockIdx.x, acc + (size_t)pair * COVIS_ACC, nullptr, nullptr);
+}
+
+// Pair p's accumulators decoded into its outputs; a pair that was never dereferenced reports count = -1.
+__device__ __forceinline__ void covis_decode(const int* __restrict__ acc, int p, bool dereferenced,
+                                             float* __restrict__ box1, float* __restrict__ box2,
+                                             uint8_t* __restrict__ valid, int32_t* __restrict__ count) {
   const int* a = acc + (size_t)p * COVIS_ACC;
-  const int n = a[A_COUNT];
+  const int n = dereferenced ? a[A_COUNT] : -1;
   const bool ok = n > 0;
   float* b1 = box1 + 4 * (size_t)p;
   float* b2 = box2 + 4 * (size_t)p;
@@ -152,15 +198,89 @@ __global__ void k_covis_finish(const int* __restrict__ acc, int n_pairs, float* 
   if (count) count[p] = n;
 }
 
+// one thread per pair
+__global__ void k_covis_finish(const int* __restrict__ acc, int n_pairs, float* __restrict__ box1,
+                               float* __restrict__ box2, uint8_t* __restrict__ valid, int32_t* __restrict__ count) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  covis_decode(acc, p, true, box1, box2, valid, count);
+}
+
+// one thread per pair; the test k_covis_warp_indexed made, made again
+__global__ void k_covis_finish_indexed(const oetr_covis_map* __restrict__ maps, int n_maps,
+                                       const int32_t* __restrict__ idx1, const int32_t* __restrict__ idx2,
+                                       int max_pixels, const int* __restrict__ acc, int n_pairs,
+                                       float* __restrict__ box1, float* __restrict__ box2,
+                                       uint8_t* __restrict__ valid, int32_t* __restrict__ count) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  oetr_covis_map a, b;
+  covis_decode(acc, p, covis_pair_maps(maps, n_maps, idx1, idx2, p, max_pixels, a, b), box1, box2, valid, count);
+}
+
+constexpr int SELECT_THREADS = 256;
+
+// Python's max(a, b): a unless b > a (a NaN first argument stays, a NaN second one is dropped)
+__device__ __forceinline__ double py_max(double a, double b) { return b > a ? b : a; }
+
+// ONE workgroup: chunks of SELECT_THREADS pairs in list order; within a chunk the kept pairs are numbered by a
+// ballot per wave and a running sum over the waves, so the kept list is ascending whatever the scheduling.
+__global__ __launch_bounds__(SELECT_THREADS) void k_covis_select(const float* __restrict__ box1,
+                                                                 const float* __restrict__ box2,
+                                                                 const uint8_t* __restrict__ valid, int n_pairs,
+                                                                 double min_scale_diff, int limit,
+                                                                 int32_t* __restrict__ kept, int32_t* __restrict__ n_kept,
+                                                                 double* __restrict__ scale_diff) {
+  constexpr int WAVES = SELECT_THREADS / 64;
+  __shared__ int wave_kept[WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int cut = limit > 0 ? limit : n_pairs;
+  int total = 0;                                                  // kept so far (uncut); the same in every thread
+  for (int base = 0; base < n_pairs; base += SELECT_THREADS) {
+    const int p = base + (int)threadIdx.x;
+    bool keep = false;
+    if (p < n_pairs) {
+      const float* a = box1 + 4 * (size_t)p;
+      const float* b = box2 + 4 * (size_t)p;
+      const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
+      const double w_diff = py_max((a2 - a0) / (b2 - b0), (b2 - b0) / (a2 - a0));
+      const double h_diff = py_max((a3 - a1) / (b3 - b1), (b3 - b1) / (a3 - a1));
+      const double sd = py_max(w_diff, h_diff);
+      if (scale_diff) scale_diff[p] = sd;
+      const double top_a = fmax(fmax(a0, a1), fmax(a2, a3)), top_b = fmax(fmax(b0, b1), fmax(b2, b3));
+      keep = valid[p] != 0 && top_a > 0.0 && top_b > 0.0 && sd > min_scale_diff;
+    }
+    const unsigned long long votes = __ballot(keep);
+    if (lane == 0) wave_kept[wave] = __popcll(votes);
+    __syncthreads();
+    int before = total, chunk = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      if (w < wave) before += wave_kept[w];
+      chunk += wave_kept[w];
+    }
+    const int at = before + __popcll(votes & ((1ull << lane) - 1ull));
+    if (keep && at < cut) kept[at] = p;
+    total += chunk;
+    __syncthreads();                                              // wave_kept is rewritten by the next chunk
+  }
+  const int written = total < cut ? total : cut;
+  for (int k = written + (int)threadIdx.x; k < n_pairs; k += SELECT_THREADS) kept[k] = -1;
+  if (threadIdx.x == 0) *n_kept = written;
+}
+
 namespace {
 
-oetr_status covis_fail(oetr_status st, const std::string& msg) {
-  return (oetr_status)set_last_error(st, ("oetr_covis_boxes: " + msg).c_str());
+oetr_status covis_fail(oetr_status st, const std::string& msg, const char* entry = "oetr_covis_boxes") {
+  return (oetr_status)set_last_error(st, (std::string(entry) + ": " + msg).c_str());
 }
 
-oetr_status covis_hip(hipError_t e, const char* what) {
-  return e == hipSuccess ? OETR_OK : covis_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+oetr_status covis_hip(hipError_t e, const char* what, const char* entry = "oetr_covis_boxes") {
+  return e == hipSuccess ? OETR_OK
+                         : covis_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), entry);
 }
+
+constexpr int COVIS_MAX_GRID_Y = 65535;                           // the grid's y extent: more pairs, more launches
 
 }  // namespace
 }  // namespace oetr
@@ -197,7 +317,7 @@ oetr_status oetr_covis_boxes(const float* depth1, const float* depth2, const dou
     if (oetr_status rc = covis_hip(hipMemsetAsync(mask1, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask1)")) return rc;
     if (oetr_status rc = covis_hip(hipMemsetAsync(mask2, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask2)")) return rc;
   }
-  constexpr int max_pairs = 65535;                                // the grid's y extent: more pairs, more launches
+  constexpr int max_pairs = COVIS_MAX_GRID_Y;
   const unsigned blocks = (unsigned)((n_pix + COVIS_PIX - 1) / COVIS_PIX);
   for (int p0 = 0; p0 < n_pairs; p0 += max_pairs) {
     const int n = n_pairs - p0 < max_pairs ? n_pairs - p0 : max_pairs;
@@ -210,6 +330,55 @@ oetr_status oetr_covis_boxes(const float* depth1, const float* depth2, const dou
   hipLaunchKernelGGL(k_covis_finish, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, acc, n_pairs, box1,
                      box2, valid, count);
   return covis_hip(hipGetLastError(), "k_covis_finish");
+}
+
+int oetr_covis_set_abi_version(void) { return OETR_COVIS_SET_ABI_VERSION; }
+
+size_t oetr_covis_set_workspace_bytes(int n_pairs) { return oetr_covis_workspace_bytes(n_pairs); }
+
+oetr_status oetr_covis_boxes_indexed(const oetr_covis_map* maps, int n_maps, const int32_t* idx1,
+                                     const int32_t* idx2, const double* params, int n_pairs, int64_t max_pixels,
+                                     void* workspace, size_t workspace_bytes, float* box1, float* box2,
+                                     uint8_t* valid, int32_t* count, void* stream) {
+  const char* me = "oetr_covis_boxes_indexed";
+  if (!maps || !idx1 || !idx2 || !params) return covis_fail(OETR_ERR_BAD_ARG, "NULL map table / index / parameter pointer", me);
+  if (!box1 || !box2 || !valid) return covis_fail(OETR_ERR_BAD_ARG, "NULL box / valid output", me);
+  if (n_maps <= 0 || n_pairs <= 0) return covis_fail(OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0", me);
+  if (max_pixels < 1 || max_pixels > (int64_t)SIDE * SIDE)
+    return covis_fail(OETR_ERR_BAD_SHAPE, "need 1 <= max_pixels <= " + std::to_string((int64_t)SIDE * SIDE), me);
+  const size_t need = oetr_covis_set_workspace_bytes(n_pairs);
+  if (!workspace || workspace_bytes < need)
+    return covis_fail(OETR_ERR_BAD_ARG, "workspace NULL or smaller than oetr_covis_set_workspace_bytes(n_pairs) = " +
+                                            std::to_string(need), me);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* acc = static_cast<int*>(workspace);
+  if (oetr_status rc = covis_hip(hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)", me)) return rc;
+  const int max_pix = (int)max_pixels;
+  const unsigned blocks = (unsigned)((max_pix + COVIS_PIX - 1) / COVIS_PIX);
+  for (int p0 = 0; p0 < n_pairs; p0 += COVIS_MAX_GRID_Y) {
+    const int n = n_pairs - p0 < COVIS_MAX_GRID_Y ? n_pairs - p0 : COVIS_MAX_GRID_Y;
+    hipLaunchKernelGGL(k_covis_warp_indexed, dim3(blocks, (unsigned)n), dim3(COVIS_THREADS), 0, s, maps, n_maps,
+                       idx1 + p0, idx2 + p0, params + (size_t)p0 * OETR_COVIS_PARAM_DOUBLES, max_pix,
+                       acc + (size_t)p0 * COVIS_ACC);
+    if (oetr_status rc = covis_hip(hipGetLastError(), "k_covis_warp_indexed", me)) return rc;
+  }
+  hipLaunchKernelGGL(k_covis_finish_indexed, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, maps, n_maps,
+                     idx1, idx2, max_pix, acc, n_pairs, box1, box2, valid, count);
+  return covis_hip(hipGetLastError(), "k_covis_finish_indexed", me);
+}
+
+oetr_status oetr_covis_select(const float* box1, const float* box2, const uint8_t* valid, int n_pairs,
+                              double min_scale_diff, int limit, int32_t* kept, int32_t* n_kept, double* scale_diff,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  const char* me = "oetr_covis_select";
+  (void)workspace; (void)workspace_bytes;                         // reserved (include/oetr_covis_set.h)
+  if (!box1 || !box2 || !valid) return covis_fail(OETR_ERR_BAD_ARG, "NULL box / valid input", me);
+  if (!kept || !n_kept) return covis_fail(OETR_ERR_BAD_ARG, "NULL kept / n_kept output", me);
+  if (n_pairs <= 0) return covis_fail(OETR_ERR_BAD_ARG, "need n_pairs > 0", me);
+  if (std::isnan(min_scale_diff)) return covis_fail(OETR_ERR_BAD_ARG, "min_scale_diff is NaN", me);
+  hipLaunchKernelGGL(k_covis_select, dim3(1), dim3(SELECT_THREADS), 0, static_cast<hipStream_t>(stream), box1, box2,
+                     valid, n_pairs, min_scale_diff, limit, kept, n_kept, scale_diff);
+  return covis_hip(hipGetLastError(), "k_covis_select", me);
 }
 
 }  // extern "C"

@@ -8,14 +8,16 @@ included, as in the reference - and the recall at a threshold is the share of va
 
 The ground truth comes from the batch (``overlap_box1`` / ``overlap_box2``, what the reference's
 dataset emits) or is computed on the device from depth maps, intrinsics and poses
-(``covis.overlap_boxes_from_batch``).
+(``covis.overlap_boxes_from_batch``).  ``evaluate_indexed`` scores the feature-bank route the same
+way: a pair list over an image set, the ground truth by index from a ``covis_set.DepthSet``.
 """
 import numpy as np
 import torch
 
 from .covis import overlap_boxes_from_batch
+from .covis_set import overlap_boxes_indexed
 from .losses import bbox_iou_aligned, bbox_oiou
-from .pipeline import _model_device
+from .pipeline import _model_device, forward_pairs_indexed
 
 DEFAULT_IOU_THRS = np.arange(0.5, 0.96, 0.05)
 
@@ -26,6 +28,34 @@ def count_recalls(ious, iou_thrs):
     threshold.  No host read."""
     thrs = torch.as_tensor(np.asarray(iou_thrs, dtype=np.float64), device=ious.device)
     return (ious.to(torch.float64)[:, None] >= thrs[None, :]).sum(0)
+
+
+def score_boxes(produced, iou_thrs, oiou=False, logger=None):
+    """The scoring tail both evaluators share.  ``produced``: a list of ``(gt_box1, gt_box2, valid or None,
+    pred_box1, pred_box2)`` with SETTLED float32 ``[n,4]`` boxes on one device -> the result dict of
+    :func:`evaluate_dummy`.  IoUs and the per-threshold counts stay on the device; one read."""
+    thrs = np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    if not produced:
+        return {'recalls': np.zeros(thrs.size), 'n': 0, 'mean_iou': float('nan'), 'n_valid_pairs': 0}
+    score = bbox_oiou if oiou else bbox_iou_aligned
+    ious, n_valid = [], 0
+    for gt1, gt2, valid, pred1, pred2 in produced:
+        ious += [score(gt1, pred1), score(gt2, pred2)]
+        if valid is None:
+            valid = (gt1 != 0).any(1) | (gt2 != 0).any(1)
+        n_valid = n_valid + valid.sum()
+    ious = torch.cat(ious)
+    n = int(ious.numel())
+    # counts, the IoU sum and the valid pairs in ONE float64 tensor (exact for these integers): one read
+    packed = torch.cat([count_recalls(ious, thrs).to(torch.float64), ious.to(torch.float64).nansum()[None],
+                        n_valid.to(torch.float64)[None]]).cpu().numpy()
+    recalls = packed[:thrs.size] / float(n)
+    if logger is not None and thrs.size > 8:
+        logger.info('Validation results:')
+        logger.info('Recalls\t R0.5\t R0.75\t R0.9\t')
+        logger.info('Values\t {:.5f}\t {:.5f}\t {:.5f}\t'.format(recalls[0], recalls[5], recalls[8]))
+    return {'recalls': recalls, 'n': n, 'mean_iou': float(packed[thrs.size] / n),
+            'n_valid_pairs': int(packed[thrs.size + 1])}
 
 
 @torch.no_grad()
@@ -71,24 +101,29 @@ def evaluate_dummy(model, batches, iou_thrs=DEFAULT_IOU_THRS, oiou=False, gt='au
     flush = getattr(model, 'hip_flush', None)
     if flush is not None:
         flush()
-    if not produced:
-        return {'recalls': np.zeros(thrs.size), 'n': 0, 'mean_iou': float('nan'), 'n_valid_pairs': 0}
-    score = bbox_oiou if oiou else bbox_iou_aligned
-    ious, n_valid = [], 0
-    for gt1, gt2, valid, pred1, pred2 in produced:
-        ious += [score(gt1, pred1), score(gt2, pred2)]
-        if valid is None:
-            valid = (gt1 != 0).any(1) | (gt2 != 0).any(1)
-        n_valid = n_valid + valid.sum()
-    ious = torch.cat(ious)
-    n = int(ious.numel())
-    # counts, the IoU sum and the valid pairs in ONE float64 tensor (exact for these integers): one read
-    packed = torch.cat([count_recalls(ious, thrs).to(torch.float64), ious.to(torch.float64).nansum()[None],
-                        n_valid.to(torch.float64)[None]]).cpu().numpy()
-    recalls = packed[:thrs.size] / float(n)
-    if logger is not None and thrs.size > 8:
-        logger.info('Validation results:')
-        logger.info('Recalls\t R0.5\t R0.75\t R0.9\t')
-        logger.info('Values\t {:.5f}\t {:.5f}\t {:.5f}\t'.format(recalls[0], recalls[5], recalls[8]))
-    return {'recalls': recalls, 'n': n, 'mean_iou': float(packed[thrs.size] / n),
-            'n_valid_pairs': int(packed[thrs.size + 1])}
+    return score_boxes(produced, thrs, oiou, logger)
+
+
+@torch.no_grad()
+def evaluate_indexed(model, images, depth_set, pair_index, iou_thrs=DEFAULT_IOU_THRS, oiou=False, max_batch=8,
+                     logger=None):
+    """:func:`evaluate_dummy` for a pair LIST over an image SET: the boxes by
+    ``pipeline.forward_pairs_indexed(model, images, pair_index, max_batch)`` (trunk and neck once per
+    image, mixed sizes), the ground truth by ``covis_set.overlap_boxes_indexed(depth_set, pair_index)``
+    - slot k of ``depth_set`` holds the depth map and camera of ``images[k]``, read in place.
+    ``pair_index``: a host sequence of ``(i, j)``.  Returns the same dict with the same counting (all
+    ``2 * len(pair_index)`` boxes count; ``n_valid_pairs`` from ``overlap_valid``).  The boxes are scored
+    settled - ``forward_pairs_indexed`` ends with its one ``model.hip_flush()`` - and the scoring reads the
+    device once."""
+    thrs = np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    pair_index = [(int(i), int(j)) for i, j in pair_index]
+    if not pair_index:
+        return score_boxes([], thrs, oiou, logger)
+    if len(images) != len(depth_set):
+        raise ValueError(f'{len(images)} images, {len(depth_set)} depth maps: slot k of the set must hold the depth '
+                         'map of images[k]')
+    truth = overlap_boxes_indexed(depth_set, pair_index)
+    pred1, pred2 = forward_pairs_indexed(model, images, pair_index, max_batch=max_batch)
+    to = lambda t: t.to(pred1.device, non_blocking=True)
+    return score_boxes([(to(truth['overlap_box1']), to(truth['overlap_box2']), to(truth['overlap_valid']), pred1, pred2)],
+                       thrs, oiou, logger)

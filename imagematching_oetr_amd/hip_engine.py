@@ -66,6 +66,11 @@ class _CropPair(C.Structure):
                 ('scale', (C.c_float * 2) * 2)]
 
 
+class _CovisMap(C.Structure):
+    """``oetr_covis_map`` (include/oetr_covis_set.h): one row of a depth-map set's device table."""
+    _fields_ = [('depth', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32)]
+
+
 class _CropInfo(C.Structure):
     _fields_ = [('valid', C.c_int32), ('box', (C.c_int32 * 4) * 2),
                 ('crop_w', C.c_int32 * 2), ('crop_h', C.c_int32 * 2),
@@ -113,6 +118,12 @@ FLAG_INDEX = 4       # OETR_FLAG_INDEX: a pair index was outside its bank (a cal
 COVIS_ABI_VERSION = 1
 COVIS_EXPORTS = ('oetr_covis_abi_version', 'oetr_covis_workspace_bytes', 'oetr_covis_boxes')
 COVIS_PARAM_DOUBLES = 40   # OETR_COVIS_PARAM_DOUBLES
+
+# The depth-map-set extension (include/oetr_covis_set.h): likewise
+COVIS_SET_ABI_VERSION = 1
+COVIS_SET_EXPORTS = ('oetr_covis_set_abi_version', 'oetr_covis_set_workspace_bytes', 'oetr_covis_boxes_indexed',
+                     'oetr_covis_select')
+COVIS_MAX_SIDE = 8192      # OETR_COVIS_MAX_SIDE
 
 # The batched crop extension (include/oetr_crop_batch.h): likewise
 CROP_BATCH_ABI_VERSION = 1
@@ -314,6 +325,19 @@ def load_library(path=None):
     lib.oetr_covis_boxes.argtypes = [vp, vp, vp, i, i, i, vp, sz] + [vp] * 7
     if lib.oetr_covis_abi_version() != COVIS_ABI_VERSION:
         raise RuntimeError(f'{p}: covis ABI version {lib.oetr_covis_abi_version()} != {COVIS_ABI_VERSION}')
+    # include/oetr_covis_set.h
+    lib.oetr_covis_set_abi_version.restype = i
+    lib.oetr_covis_set_abi_version.argtypes = []
+    lib.oetr_covis_set_workspace_bytes.restype = sz
+    lib.oetr_covis_set_workspace_bytes.argtypes = [i]
+    lib.oetr_covis_boxes_indexed.restype = i
+    # maps, n_maps, idx1, idx2, params, n_pairs, max_pixels, workspace, workspace_bytes, box1, box2, valid, count, stream
+    lib.oetr_covis_boxes_indexed.argtypes = [vp, i, vp, vp, vp, i, C.c_int64, vp, sz] + [vp] * 5
+    lib.oetr_covis_select.restype = i
+    # box1, box2, valid, n_pairs, min_scale_diff, limit, kept, n_kept, scale_diff, workspace, workspace_bytes, stream
+    lib.oetr_covis_select.argtypes = [vp, vp, vp, i, C.c_double, i, vp, vp, vp, vp, sz, vp]
+    if lib.oetr_covis_set_abi_version() != COVIS_SET_ABI_VERSION:
+        raise RuntimeError(f'{p}: covis-set ABI version {lib.oetr_covis_set_abi_version()} != {COVIS_SET_ABI_VERSION}')
     # include/oetr_crop_batch.h
     lib.oetr_crop_batch_abi_version.restype = i
     lib.oetr_crop_batch_abi_version.argtypes = []
