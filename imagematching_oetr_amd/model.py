@@ -268,8 +268,11 @@ class OETR(nn.Module):
             f = self.neck(self.trunk(torch.cat([image1, image2], dim=0)))
             feat1, feat2 = f[:n], f[n:]
         else:
-            feat1 = self.neck(self.trunk(image1))
-            feat2 = self.neck(self.trunk(image2))
+            bb1, bb2 = self.trunk(image1), self.trunk(image2)
+            for bb in (bb1, bb2):       # refuse before the first neck launch, whichever side is too small
+                if bb.shape[2] < 2 or bb.shape[3] < 2:
+                    raise ValueError(f'image too small: backbone map {tuple(bb.shape[2:])} gives an empty token grid')
+            feat1, feat2 = self.neck(bb1), self.neck(bb2)
         hf1, wf1 = feat1.shape[2:]
         hf2, wf2 = feat2.shape[2:]
         return (feat1, feat2, self.pos_encoding(feat1), self.pos_encoding(feat2),

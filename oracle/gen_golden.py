@@ -327,6 +327,98 @@ def gen_neck(out_dir, model):
         print(f'neck_{tag}.npz feat {tuple(feat.shape)} absmax {float(feat.abs().max()):.3f}')
 
 
+OFFGRID_CASES = [
+    # tag, image1 (h, w), image2 (h, w), shift of tlbr_reg.2.bias.  Sizes off the 32-px grid: the trunk
+    # gives hb = ceil(h/16), the neck hf = hb // 2, and center_estimation scales BOTH axes with h // hf
+    # (src/model.py:176-181) - 33 at 333 x 517 (w // wf = 32) and 100 x 75 (37), 47 at 47 x 640 (x runs to
+    # 916 > w), 32 at 641 x 639 (the control), 31 at 63 x 31, 17 at 17 x 17 (the smallest image the neck takes)
+    ('333x517_100x75', (333, 517), (100, 75), -6.0),
+    ('47x640_641x639', (47, 640), (641, 639), -6.0),
+    ('63x31_17x17', (63, 31), (17, 17), -6.0),
+    # the stock bias: extents ~0.97 of the image, x2 / y2 saturate at w / h (not at 0): pins the clamp bounds.
+    # Only tlbr and the boxes depend on the bias: the record holds those (and cxy), every other stage is the
+    # one of offgrid_47x640_641x639.npz, which it names in `stages_from`
+    ('clamp_47x640_641x639', (47, 640), (641, 639), 0.0),
+]
+OFFGRID_WEIGHT_SEED, OFFGRID_IMAGE_SEED = 6, 3
+
+
+@torch.no_grad()
+def gen_offgrid(out_dir, model):
+    """The reference's ``forward_dummy`` FROM IMAGES whose sizes are no multiples of 32 (one image per
+    side), every stage recorded: neck features, position tables (checksums), memory (row sample), hs,
+    heat-map logits, cxy, tlbr, boxes.  Weights: our module's seeded trunk and neck (strict load, as
+    gen_full) + make_hot_weights(6, sharpen=True, tlbr_bias_shift).  With shift -6 every side of every box
+    must lie strictly inside its image (asserted): a box on the clamp carries no information."""
+    import copy
+    from imagematching_oetr_amd import get_cfg_defaults as own_cfg
+    from imagematching_oetr_amd.model import OETR as OwnOETR
+    torch.manual_seed(0)
+    own_sd = OwnOETR(own_cfg().OETR).eval().state_dict()
+    for tag, hw1, hw2, shift in OFFGRID_CASES:
+        w = orc.make_hot_weights(OFFGRID_WEIGHT_SEED, sharpen=True, tlbr_bias_shift=shift)
+        sd = dict(own_sd)
+        sd.update(w)
+        model.load_state_dict(sd, strict=True)
+        g = torch.Generator().manual_seed(OFFGRID_IMAGE_SEED)
+        image1 = torch.rand(1, *hw1, 3, generator=g)
+        image2 = torch.rand(1, *hw2, 3, generator=g)
+        rec, logits = {}, []
+        names = ('feature_extraction', 'feature_correlation', 'center_estimation', 'size_regression')
+
+        def tap(name):
+            fn = getattr(model, name)
+
+            def wrapped(*a, **k):
+                rec[name] = fn(*a, **k)
+                return rec[name]
+            setattr(model, name, wrapped)       # an instance attribute in front of the method
+        for name in names:
+            tap(name)
+        hk = model.heatmap_conv.register_forward_hook(
+            lambda _m, _i, out: logits.append(out.detach().flatten(1).clone()))
+        b1, b2 = model.forward_dummy(image1, image2)
+        hk.remove()
+        for name in names:
+            delattr(model, name)
+        f1, f2, p1, p2, hf1, wf1, hf2, wf2 = rec['feature_extraction']
+        hs1, hs2, m1, m2 = rec['feature_correlation']
+        (c1, c2), (t1, t2) = rec['center_estimation'], rec['size_regression']
+        assert (hf1, wf1) == (-(-hw1[0] // 16) // 2, -(-hw1[1] // 16) // 2), (hf1, wf1)
+        for b, (h, ww) in ((b1, hw1), (b2, hw2)):
+            if shift:
+                assert (b > 0).all() and (b[:, 0::2] < ww).all() and (b[:, 1::2] < h).all(), (tag, b, h, ww)
+            else:
+                assert (b[:, 2] == ww).all() and (b[:, 3] == h).all(), (tag, b, h, ww)
+        # the reference's own fp32 error on the features: the same modules in double precision
+        m64 = copy.deepcopy(model).double()
+        d1, d2 = m64.feature_extraction(image1.double(), image2.double())[:2]
+        drift = max(float((f1.double() - d1).abs().max()), float((f2.double() - d2).abs().max()))
+        data = dict(weight_seed=np.int64(OFFGRID_WEIGHT_SEED), sharpen=np.bool_(True),
+                    tlbr_bias_shift=np.float64(shift), image_seed=np.int64(OFFGRID_IMAGE_SEED),
+                    n=np.int64(1), grid1=np.asarray((hf1, wf1)), grid2=np.asarray((hf2, wf2)),
+                    img1=np.asarray(hw1), img2=np.asarray(hw2),
+                    image1_fp=fp(image1), image2_fp=fp(image2),
+                    weights_fp=fp(torch.cat([w[k].flatten() for k in sorted(w)])),
+                    feat1=f1.numpy(), feat2=f2.numpy(), feat_fp64_drift=np.float64(drift),
+                    pos1_fp=fp(p1), pos2_fp=fp(p2),
+                    hs1=hs1.numpy(), hs2=hs2.numpy(), logits1=logits[0].numpy(), logits2=logits[1].numpy(),
+                    cxy1=c1.numpy(), cxy2=c2.numpy(), tlbr1=t1.numpy(), tlbr2=t2.numpy(),
+                    box1=b1.numpy(), box2=b2.numpy())
+        data['memory1'], data['memory1_step'] = sub(m1)
+        data['memory2'], data['memory2_step'] = sub(m2)
+        if not shift:       # the stages ahead of the tlbr head are recorded once, by the shifted case of these images
+            base = np.load(out_dir / f'offgrid_{tag[len("clamp_"):]}.npz')
+            shared = [k for k in data if k[:-1] in ('feat', 'hs', 'logits', 'cxy') or k.startswith('memory') or k == 'feat_fp64_drift']
+            for k in shared:
+                assert np.array_equal(data[k], base[k]), (tag, k)
+            data = {k: v for k, v in data.items() if k not in shared or k.startswith('cxy')}
+            data['stages_from'] = np.asarray(f'offgrid_{tag[len("clamp_"):]}.npz')
+        np.savez_compressed(out_dir / f'offgrid_{tag}.npz', **data)
+        print(f'offgrid_{tag}.npz grids {(hf1, wf1)} {(hf2, wf2)} cxy1 {c1[0].tolist()} box1 {b1[0].tolist()} '
+              f'cxy2 {c2[0].tolist()} box2 {b2[0].tolist()} feat fp64 drift {drift:.2e}')
+
+
 def gen_misc(out_dir):
     """Position table window, box conversion and the reference's only
     known-answer vectors (bbox_overlaps docstring, src/losses/utils.py:31-53)."""
@@ -580,6 +672,8 @@ def main():
         return gen_train_forward(out_dir, build_reference_model())
     if args.only == 'hot':
         return gen_hot(out_dir, build_reference_model())
+    if args.only == 'offgrid':
+        return gen_offgrid(out_dir, build_reference_model())
     if args.only == 'mask':
         gen_attention_masked(out_dir)
         return gen_hot(out_dir, build_reference_model(), MASK_CASES, 'hotmask_')
@@ -597,6 +691,8 @@ def main():
     # a FRESH reference model: gen_neck has loaded seeded neck weights into `model`, and the
     # committed train_forward.npz is what `--only train` (fresh model) produces
     gen_train_forward(out_dir, build_reference_model())
+    # written last, into a fresh model as well: nothing above sees its weights
+    gen_offgrid(out_dir, build_reference_model())
 
 
 if __name__ == '__main__':

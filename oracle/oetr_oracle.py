@@ -80,7 +80,7 @@ def hot_path_param_shapes():
     return s
 
 
-def make_hot_weights(seed, sharpen=False):
+def make_hot_weights(seed, sharpen=False, tlbr_bias_shift=0.0):
     """Deterministic synthetic hot-path weights built from ``torch.rand`` only
     (uniform draws from the CPU mt19937 stream are bit-reproducible across
     machines; normal draws go through vectorised libm and are not relied on).
@@ -91,7 +91,10 @@ def make_hot_weights(seed, sharpen=False):
     ``sharpen`` rescales the two head output layers (heat-map 1x1 conv x8,
     tlbr output x0.35) so that soft-argmax is moderately peaked and the
     sigmoid stays off saturation - the regime where boxes actually depend on
-    the inputs (random-init boxes are nearly input-blind)."""
+    the inputs (random-init boxes are nearly input-blind).
+    ``tlbr_bias_shift`` is added to ``tlbr_reg.2.bias``: with the stock bias the four
+    extents are ~0.5 .. 0.97 of the image and a box from a whole image saturates at the
+    clamp; -6 brings them to a few percent, so that every side stays inside the image."""
     g = torch.Generator().manual_seed(int(seed))
     w = {}
     for name, shape in hot_path_param_shapes().items():
@@ -109,6 +112,8 @@ def make_hot_weights(seed, sharpen=False):
     if sharpen:
         w['heatmap_conv.3.weight'] = w['heatmap_conv.3.weight'] * 8.0
         w['tlbr_reg.2.weight'] = w['tlbr_reg.2.weight'] * 0.35
+    if tlbr_bias_shift:
+        w['tlbr_reg.2.bias'] = w['tlbr_reg.2.bias'] + float(tlbr_bias_shift)
     return w
 
 

@@ -3,6 +3,7 @@ SURVEY.md §8f.1) through the C ABI, against the reference goldens and the
 oracle.  Tolerance: the reference's own fp32-vs-fp64 drift on ``feat`` is
 ~5e-6 (abs-max 5.7); the bound below is 10x that."""
 import glob
+import re
 from pathlib import Path
 
 import numpy as np
@@ -133,3 +134,55 @@ def test_module_neck_hip_vs_torch_modules(gpu):
     with torch.no_grad():
         model.input_proj2.bias.add_(0.5)
     assert (model.neck(bb) - hip - 0.5).abs().max().item() <= 1e-5
+
+
+# backbone maps of images off the 32-px grid (hb = ceil(h/16)): 333 x 517, 100 x 75, 47 x 640, 641 x 639, an odd
+# row count the neck drops (PatchMerging keeps floor(hb/2) rows), the smallest map with an odd width, a tall one
+ODD_MAPS = [(2, 21, 33), (1, 7, 5), (3, 3, 40), (1, 41, 40), (2, 2, 3), (1, 99, 41)]
+# the narrowest output map the row-window conv kernels take: read from the kernels' own header, so that the
+# widths below follow it (a renamed or removed constant fails here, at import)
+NECK_RW_MIN_WO = int(re.search(r'constexpr int NECK_RW_MIN_WO = (\d+);',
+                               (Path(pkg.__file__).parent / 'csrc' / 'common.h').read_text()).group(1))
+assert any(wb // 2 == NECK_RW_MIN_WO for _, _, wb in ODD_MAPS), 'no odd map at the row-window kernels\' narrowest width'
+
+
+@pytest.fixture(scope='module')
+def odd_maps():
+    """Weights, inputs and the fp64 oracle per map (computed once)."""
+    w = orc.make_neck_weights(49)
+    w64 = {k: v.double() for k, v in w.items()}
+    made = {}
+
+    def get(n, hb, wb):
+        if (n, hb, wb) not in made:
+            bb = orc.make_backbone_features(50 + hb, n, hb, wb)
+            made[(n, hb, wb)] = bb, orc.neck(bb.double(), w64)
+        return (w,) + made[(n, hb, wb)]
+    return get
+
+
+@pytest.mark.parametrize('n,hb,wb', ODD_MAPS)
+def test_neck_token_store_at_odd_maps(gpu, odd_maps, n, hb, wb):
+    """oetr_neck_forward_tokens stores what oetr_neck_forward computes, token-major
+    (``flatten(2).permute(0, 2, 1)``), bit for bit - under each conv kernel the width allows, and into a
+    buffer with guard rows before and after, which come back untouched.  The NCHW result is the fp64
+    oracle's at FEAT_TOL."""
+    w, bb, ref = odd_maps(n, hb, wb)
+    ho, wo = hb // 2, wb // 2
+    rows = n * ho * wo
+    eng = pkg.NeckEngine(w, device=gpu)
+    x = bb.to(gpu)
+    kinds = ['auto', 'gather'] + (['row_window', 'row_window_1w'] if wo >= NECK_RW_MIN_WO else [])
+    guard, fill = 3, -7.25
+    for kind in kinds:
+        eng.set_conv_kernel(kind)
+        feat = eng.forward(x)
+        assert feat.shape == (n, 256, ho, wo)
+        err = (feat.cpu().double() - ref).abs().max().item()
+        assert err <= FEAT_TOL, f'{kind}: feat max err {err:.3e}'
+        want = feat.flatten(2).permute(0, 2, 1).reshape(rows, 256)
+        buf = torch.full((rows + 2 * guard, 256), fill, device=gpu)
+        eng.forward_tokens(x, buf[guard:guard + rows])
+        assert torch.equal(buf[guard:guard + rows], want), f'{kind}: token store differs from the NCHW result'
+        assert (buf[:guard] == fill).all() and (buf[guard + rows:] == fill).all(), f'{kind}: guard rows written'
+        assert eng.query_flags() == 0
