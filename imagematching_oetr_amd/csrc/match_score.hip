@@ -1,0 +1,307 @@
+// Scoring matches against depth and pose (include/oetr_match_score.h): the reference's compute_epipolar_error,
+// get_episym and get_projected_kp + get_truesym for many match lists over a depth-map set, in one call.
+//
+// k_match_score: one thread per match row, 256-thread workgroups.  The row finds its list by binary search in the
+// offsets (largest p with offsets[p] <= m, scored only if m < offsets[p+1]), makes the vouching test of
+// k_covis_warp_indexed on its pair's two table rows (without max_pixels: the grid is over matches) and then runs
+// tests/match_score_oracle.py::score LITERALLY: float64, every operation rounded on its own in the order and with
+// the parentheses written there (no contraction into FMAs: rint() and the "<" tests are discontinuous and the
+// parity target is a float64 numpy program).  E = [t]x R, m = R^T t and px_thr * px_thr are computed per thread
+// with the same individual operations.  Twelve float64 divisions per row.  The search is made ONCE PER WAVE for the
+// wave's first row, with scalar loads; a wave whose rows all lie in that list - the common case - also takes its two
+// indices, two table rows and 20 parameters by scalar loads, so that a row's chain of dependent VECTOR loads is its
+// keypoints and its two depth pixels.  (A search and the pair's data per lane, 16 dependent vector loads, cost 6.4x
+// a copy of the call's bytes; profiles/match_score_probe.json has what this form costs.)  Lanes past the first
+// row's list search for themselves, and such a wave loads per lane.
+// Nothing is dereferenced on the strength of device data alone: a row index is below the host's n_matches, a pair
+// number inside [0, n_pairs) by construction of the search, a map index tested against n_maps, a depth pixel
+// tested in float64 against its row's H, W before the conversion to an integer.
+//
+// Counters: a wave whose counted rows all belong to one pair takes one ballot and one popcount per flag and
+// issues one atomicAdd per non-zero counter; a wave that straddles lists falls back to per-lane atomicAdd.
+// Integer atomics commute: the counters do not depend on arrival order.  k_match_clear zeroes the counters before,
+// k_match_finish (one thread per pair) afterwards writes the list length, -1 for a threshold that is off, and -1 throughout
+// for a pair that is not vouched for.
+#include <cmath>
+#include <string>
+
+#include "../../include/oetr_match_score.h"
+#include "common.h"
+
+namespace oetr {
+
+constexpr int MATCH_THREADS = 256;
+constexpr int MATCH_PARAMS = OETR_MATCH_SCORE_PARAM_DOUBLES;
+constexpr int MATCH_COUNTERS = OETR_MATCH_SCORE_COUNTERS;
+constexpr int MATCH_SIDE = OETR_COVIS_MAX_SIDE;
+
+__device__ __forceinline__ bool match_map_usable(const oetr_covis_map& m) {
+  return m.depth != nullptr && m.H >= 1 && m.H <= MATCH_SIDE && m.W >= 1 && m.W <= MATCH_SIDE;
+}
+
+// Both table rows of pair p, or false when the pair must not be dereferenced.
+__device__ __forceinline__ bool match_pair_maps(const oetr_covis_map* __restrict__ maps, int n_maps,
+                                                const int32_t* __restrict__ idx1, const int32_t* __restrict__ idx2,
+                                                int p, oetr_covis_map& a, oetr_covis_map& b) {
+  const int i1 = idx1[p], i2 = idx2[p];
+  if (i1 < 0 || i1 >= n_maps || i2 < 0 || i2 >= n_maps) return false;
+  a = maps[i1];
+  b = maps[i2];
+  return match_map_usable(a) && match_map_usable(b);
+}
+
+// Depth at (rint(v), rint(u)), half to even, 0 outside the map.  The range test is made in float64 on the rounded
+// coordinates: NaN and +-inf fail it, -0 passes; only then is anything converted to an integer.
+__device__ __forceinline__ double match_depth_at(const oetr_covis_map& m, double u, double v) {
+#pragma clang fp contract(off)
+  const double c = rint(u), r = rint(v);
+  if (!(c >= 0.0 && c < (double)m.W && r >= 0.0 && r < (double)m.H)) return 0.0;
+  return (double)m.depth[(size_t)(int)r * (size_t)m.W + (size_t)(int)c];
+}
+
+// The largest p in [0, n_pairs) with offsets[p] <= m, or -1: the number of such entries, less one (the offsets are
+// assumed non-decreasing).  Reads offsets[0 .. n_pairs-1] only.
+__device__ __forceinline__ int match_find_list(const int32_t* __restrict__ offsets, int n_pairs, int m) {
+  int lo = 0, hi = n_pairs;
+  while (lo < hi) {
+    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);     // lo <= mid < hi <= n_pairs
+    if (offsets[mid] <= m) lo = mid + 1; else hi = mid;
+  }
+  return lo - 1;
+}
+
+struct MatchRow {
+  double epi, sym, r12, r21;
+  unsigned flag;
+};
+
+// One row of tests/match_score_oracle.py::score under the 20 doubles at P, the two maps of its pair.  The one copy
+// of the arithmetic; inlined twice (pair data by scalar loads / by per-lane loads).
+__device__ __forceinline__ MatchRow match_row(const oetr_covis_map& ma, const oetr_covis_map& mb,
+                                              const double* __restrict__ P, double u1, double v1, double u2,
+                                              double v2, double epi_thr, double sym_thr, double px_thr) {
+#pragma clang fp contract(off)
+  const double fx1 = P[0], fy1 = P[1], cx1 = P[2], cy1 = P[3], fx2 = P[4], fy2 = P[5], cx2 = P[6], cy2 = P[7];
+  const double R00 = P[8], R01 = P[9], R02 = P[10], R10 = P[11], R11 = P[12], R12 = P[13], R20 = P[14],
+               R21 = P[15], R22 = P[16];
+  const double t0 = P[17], t1 = P[18], t2 = P[19];
+
+  const double x1 = (u1 - cx1) / fx1, y1 = (v1 - cy1) / fy1;
+  const double x2 = (u2 - cx2) / fx2, y2 = (v2 - cy2) / fy2;
+  const double E00 = t1 * R20 - t2 * R10, E01 = t1 * R21 - t2 * R11, E02 = t1 * R22 - t2 * R12;
+  const double E10 = t2 * R00 - t0 * R20, E11 = t2 * R01 - t0 * R21, E12 = t2 * R02 - t0 * R22;
+  const double E20 = t0 * R10 - t1 * R00, E21 = t0 * R11 - t1 * R01, E22 = t0 * R12 - t1 * R02;
+  const double a0 = (E00 * x1 + E01 * y1) + E02;
+  const double a1 = (E10 * x1 + E11 * y1) + E12;
+  const double a2 = (E20 * x1 + E21 * y1) + E22;
+  const double b0 = (E00 * x2 + E10 * y2) + E20;
+  const double b1 = (E01 * x2 + E11 * y2) + E21;
+  const double s = (x2 * a0 + y2 * a1) + a2;
+  const double s2 = s * s;
+  MatchRow out;
+  out.epi = s2 * (1.0 / (a0 + a1) + 1.0 / (b0 + b1));
+  out.sym = s2 * (1.0 / (a0 * a0 + a1 * a1) + 1.0 / (b0 * b0 + b1 * b1));
+
+  const double d1 = match_depth_at(ma, u1, v1), d2 = match_depth_at(mb, u2, v2);
+  const double X1 = x1 * d1, Y1 = y1 * d1;
+  const double p0 = ((R00 * X1 + R01 * Y1) + R02 * d1) + t0;
+  const double p1 = ((R10 * X1 + R11 * Y1) + R12 * d1) + t1;
+  const double p2 = ((R20 * X1 + R21 * Y1) + R22 * d1) + t2;
+  const double e0 = (fx2 * (p0 / p2) + cx2) - u2, e1 = (fy2 * (p1 / p2) + cy2) - v2;
+  out.r12 = e0 * e0 + e1 * e1;
+  const double m0 = (R00 * t0 + R10 * t1) + R20 * t2;
+  const double m1 = (R01 * t0 + R11 * t1) + R21 * t2;
+  const double m2 = (R02 * t0 + R12 * t1) + R22 * t2;
+  const double X2 = x2 * d2, Y2 = y2 * d2;
+  const double q0 = ((R00 * X2 + R10 * Y2) + R20 * d2) - m0;
+  const double q1 = ((R01 * X2 + R11 * Y2) + R21 * d2) - m1;
+  const double q2 = ((R02 * X2 + R12 * Y2) + R22 * d2) - m2;
+  const double g0 = (fx1 * (q0 / q2) + cx1) - u1, g1 = (fy1 * (q1 / q2) + cy1) - v1;
+  out.r21 = g0 * g0 + g1 * g1;
+
+  const bool has1 = d1 != 0.0, has2 = d2 != 0.0;
+  const bool both = has1 && has2;
+  const bool ok_epi = out.epi < epi_thr, ok_sym = out.sym < sym_thr;   // false for a NaN threshold
+  const bool ok_px = both && (out.r21 < px_thr * px_thr);
+  out.flag = (has1 ? OETR_MATCH_DEPTH1 : 0) | (has2 ? OETR_MATCH_DEPTH2 : 0) | (ok_epi ? OETR_MATCH_EPI : 0) |
+             (ok_sym ? OETR_MATCH_EPISYM : 0) | (ok_px ? OETR_MATCH_REPROJ : 0);
+  return out;
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_match_score(
+    const oetr_covis_map* __restrict__ maps, int n_maps, const int32_t* __restrict__ idx1,
+    const int32_t* __restrict__ idx2, const double* __restrict__ params, const int32_t* __restrict__ offsets,
+    int n_pairs, const float* __restrict__ k1, const float* __restrict__ k2, int n_matches, double epi_thr,
+    double sym_thr, double px_thr, double* __restrict__ values, uint8_t* __restrict__ flags,
+    int32_t* __restrict__ counts) {
+  const int64_t row = (int64_t)blockIdx.x * MATCH_THREADS + (int64_t)threadIdx.x;
+  const bool active = row < (int64_t)n_matches;
+  const int m = active ? (int)row : 0;
+
+  // the keypoints depend on the row alone: their loads go out before the search
+  float u1 = 0.0f, v1 = 0.0f, u2 = 0.0f, v2 = 0.0f;
+  if (active) {
+    const size_t at = 2 * (size_t)m;
+    u1 = k1[at], v1 = k1[at + 1], u2 = k2[at], v2 = k2[at + 1];
+  }
+
+  // The list of the wave's FIRST row, searched once per wave with wave-uniform (scalar) loads; rows ascend with the
+  // lane, so for non-decreasing offsets a later row m < offsets[p0 + 1] belongs to p0 too: offsets[p0] <= row0 <= m
+  // and every later offset is > m.  Only a lane past that boundary searches for itself.
+  const int64_t row0 = (int64_t)blockIdx.x * MATCH_THREADS + (int64_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x);
+  int p0 = -1, end0 = 0;
+  if (row0 < (int64_t)n_matches) {
+    p0 = __builtin_amdgcn_readfirstlane(match_find_list(offsets, n_pairs, (int)row0));
+    if (p0 >= 0) end0 = offsets[p0 + 1];                            // p0 + 1 <= n_pairs
+  }
+  int p = -1;
+  if (active) {
+    if (p0 >= 0 && m < end0) {
+      p = p0;
+    } else {
+      p = match_find_list(offsets, n_pairs, m);
+      if (p >= 0 && !(m < offsets[p + 1])) p = -1;
+    }
+  }
+
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  MatchRow r = {nan, nan, nan, nan, 0u};
+  int counted = -1;                                                 // the pair this row's flags count for, or none
+  oetr_covis_map ma, mb;
+  if (__ballot(active && p != p0) == 0ull) {
+    // every active row of the wave is in list p0: indices, table rows and parameters by scalar loads
+    if (p0 >= 0 && match_pair_maps(maps, n_maps, idx1, idx2, p0, ma, mb) && active) {
+      r = match_row(ma, mb, params + (size_t)p0 * MATCH_PARAMS, (double)u1, (double)v1, (double)u2, (double)v2,
+                    epi_thr, sym_thr, px_thr);
+      counted = p0;
+    }
+  } else if (p >= 0 && match_pair_maps(maps, n_maps, idx1, idx2, p, ma, mb)) {
+    r = match_row(ma, mb, params + (size_t)p * MATCH_PARAMS, (double)u1, (double)v1, (double)u2, (double)v2, epi_thr,
+                  sym_thr, px_thr);
+    counted = p;
+  }
+  const double epi = r.epi, sym = r.sym, r12 = r.r12, r21 = r.r21;
+  const unsigned flag = r.flag;
+
+  if (active) {
+    if (values) {
+      const size_t n = (size_t)n_matches;
+      values[(size_t)m] = epi;
+      values[n + (size_t)m] = sym;
+      values[2 * n + (size_t)m] = r12;
+      values[3 * n + (size_t)m] = r21;
+    }
+    flags[m] = (uint8_t)flag;
+  }
+
+  // counters 1..4 (counter 0, the list length, is k_match_finish's).  Every lane of the wave arrives here.
+  const bool c_epi = (flag & OETR_MATCH_EPI) != 0, c_sym = (flag & OETR_MATCH_EPISYM) != 0;
+  const bool c_both = (flag & 3u) == 3u, c_px = (flag & OETR_MATCH_REPROJ) != 0;
+  const unsigned long long counting = __ballot(counted >= 0);
+  if (counting == 0ull) return;                                     // wave-uniform
+  const int first = __shfl(counted, __ffsll((long long)counting) - 1, 64);
+  const bool one_pair = __ballot(counted >= 0 && counted != first) == 0ull;
+  if (one_pair) {
+    const int n_epi = __popcll(__ballot(c_epi)), n_sym = __popcll(__ballot(c_sym));
+    const int n_both = __popcll(__ballot(c_both)), n_px = __popcll(__ballot(c_px));
+    if ((threadIdx.x & 63) == 0) {
+      int32_t* c = counts + (size_t)first * MATCH_COUNTERS;         // 0 <= first < n_pairs
+      if (n_epi) atomicAdd(c + 1, n_epi);
+      if (n_sym) atomicAdd(c + 2, n_sym);
+      if (n_both) atomicAdd(c + 3, n_both);
+      if (n_px) atomicAdd(c + 4, n_px);
+    }
+  } else if (counted >= 0) {
+    int32_t* c = counts + (size_t)counted * MATCH_COUNTERS;
+    if (c_epi) atomicAdd(c + 1, 1);
+    if (c_sym) atomicAdd(c + 2, 1);
+    if (c_both) atomicAdd(c + 3, 1);
+    if (c_px) atomicAdd(c + 4, 1);
+  }
+}
+
+// counts = 0, as a kernel of the library's own: see the note on hipMemsetAsync in oetr_match_score below
+__global__ void k_match_clear(int32_t* __restrict__ counts, int n) {
+  const unsigned at = blockIdx.x * blockDim.x + threadIdx.x;
+  if (at < (unsigned)n) counts[at] = 0;
+}
+
+// one thread per pair; the vouching test k_match_score made, made again
+__global__ void k_match_finish(const oetr_covis_map* __restrict__ maps, int n_maps, const int32_t* __restrict__ idx1,
+                               const int32_t* __restrict__ idx2, const int32_t* __restrict__ offsets, int n_pairs,
+                               int n_matches, double epi_thr, double sym_thr, double px_thr,
+                               int32_t* __restrict__ counts) {
+  const unsigned at = blockIdx.x * blockDim.x + threadIdx.x;
+  if (at >= (unsigned)n_pairs) return;
+  const int p = (int)at;
+  int32_t* c = counts + (size_t)p * MATCH_COUNTERS;
+  oetr_covis_map a, b;
+  if (!match_pair_maps(maps, n_maps, idx1, idx2, p, a, b)) {
+#pragma unroll
+    for (int k = 0; k < MATCH_COUNTERS; ++k) c[k] = -1;
+    return;
+  }
+  long long len = (long long)offsets[p + 1] - (long long)offsets[p];
+  len = len < 0 ? 0 : (len > (long long)n_matches ? (long long)n_matches : len);
+  c[0] = (int32_t)len;
+  if (epi_thr != epi_thr) c[1] = -1;
+  if (sym_thr != sym_thr) c[2] = -1;
+  if (px_thr != px_thr) c[4] = -1;
+}
+
+namespace {
+
+oetr_status match_fail(oetr_status st, const std::string& msg) {
+  return (oetr_status)set_last_error(st, ("oetr_match_score: " + msg).c_str());
+}
+
+oetr_status match_hip(hipError_t e, const char* what) {
+  return e == hipSuccess ? OETR_OK : match_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+}  // namespace
+}  // namespace oetr
+
+using namespace oetr;
+
+extern "C" {
+
+int oetr_match_score_abi_version(void) { return OETR_MATCH_SCORE_ABI_VERSION; }
+
+// The host code dereferences none of its pointer arguments and reads nothing from the device.
+oetr_status oetr_match_score(const oetr_covis_map* maps, int n_maps, const int32_t* idx1, const int32_t* idx2,
+                             const double* params, const int32_t* offsets, int n_pairs, const float* k1,
+                             const float* k2, int64_t n_matches, double epi_thr, double sym_thr, double px_thr,
+                             double* values, uint8_t* flags, int32_t* counts, void* stream) {
+  if (!maps || !idx1 || !idx2 || !params || !offsets)
+    return match_fail(OETR_ERR_BAD_ARG, "NULL map table / index / parameter / offsets pointer");
+  if (!counts) return match_fail(OETR_ERR_BAD_ARG, "NULL counts output");
+  if (n_matches != 0 && (!k1 || !k2)) return match_fail(OETR_ERR_BAD_ARG, "NULL keypoint pointer");
+  if (n_matches != 0 && !flags) return match_fail(OETR_ERR_BAD_ARG, "NULL flags output");
+  if (n_maps <= 0 || n_pairs <= 0) return match_fail(OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0");
+  if (n_matches < 0) return match_fail(OETR_ERR_BAD_ARG, "need n_matches >= 0");
+  if (n_pairs > INT32_MAX / MATCH_COUNTERS)
+    return match_fail(OETR_ERR_BAD_SHAPE, "need n_pairs <= " + std::to_string(INT32_MAX / MATCH_COUNTERS));
+  if (n_matches > (int64_t)INT32_MAX)
+    return match_fail(OETR_ERR_BAD_SHAPE, "need n_matches <= " + std::to_string(INT32_MAX) + " (the offsets are int32)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = (int)n_matches;
+  // The counters are cleared by a kernel, not by hipMemsetAsync: captured into a HIP graph as a memset node (280
+  // bytes for 14 pairs), the clearing wrote a foreign 16-byte pattern over counts on the graph's SECOND replay, after
+  // device copies had run between the replays (tests/test_gpu_match_score.py, the capture test; the runtime's side
+  // of it was not examined).  A kernel node carries its arguments with it.
+  const int n_counters = n_pairs * MATCH_COUNTERS;                  // n_pairs <= INT32_MAX / 5, checked above
+  hipLaunchKernelGGL(k_match_clear, dim3((unsigned)((n_counters + 255) / 256)), dim3(256), 0, s, counts, n_counters);
+  if (oetr_status rc = match_hip(hipGetLastError(), "k_match_clear")) return rc;
+  if (n > 0) {
+    const unsigned blocks = (unsigned)(((int64_t)n + MATCH_THREADS - 1) / MATCH_THREADS);
+    hipLaunchKernelGGL(k_match_score, dim3(blocks), dim3(MATCH_THREADS), 0, s, maps, n_maps, idx1, idx2, params,
+                       offsets, n_pairs, k1, k2, n, epi_thr, sym_thr, px_thr, values, flags, counts);
+    if (oetr_status rc = match_hip(hipGetLastError(), "k_match_score")) return rc;
+  }
+  hipLaunchKernelGGL(k_match_finish, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, maps, n_maps, idx1,
+                     idx2, offsets, n_pairs, n, epi_thr, sym_thr, px_thr, counts);
+  return match_hip(hipGetLastError(), "k_match_finish");
+}
+
+}  // extern "C"

@@ -10,6 +10,8 @@ The ground truth comes from the batch (``overlap_box1`` / ``overlap_box2``, what
 dataset emits) or is computed on the device from depth maps, intrinsics and poses
 (``covis.overlap_boxes_from_batch``).  ``evaluate_indexed`` scores the feature-bank route the same
 way: a pair list over an image set, the ground truth by index from a ``covis_set.DepthSet``.
+``match_precision`` summarises ``match_score.score_matches``: the reference's ``validation_error``
+precision per pair, from one read of the counters.
 """
 import numpy as np
 import torch
@@ -127,3 +129,37 @@ def evaluate_indexed(model, images, depth_set, pair_index, iou_thrs=DEFAULT_IOU_
     to = lambda t: t.to(pred1.device, non_blocking=True)
     return score_boxes([(to(truth['overlap_box1']), to(truth['overlap_box2']), to(truth['overlap_valid']), pred1, pred2)],
                        thrs, oiou, logger)
+
+
+def match_precision(result):
+    """The reference's ``validation_error`` summary (``dloc/evaluate/utils/evaluation.py``) of a
+    ``match_score.score_matches`` result, from ONE device read of its ``counts`` int32 ``[P,5]``
+    (a tensor or an array of that shape is taken as well).  Per pair ``precision`` = the matches with
+    ``epi_ref < epi_thr`` over the matches, 0 for an empty list as in the reference; pairs the set did
+    not vouch for (all counters -1) are EXCLUDED - NaN in the per-pair arrays - and counted in
+    ``n_not_scored``.  ``reproj_precision`` is the same for the re-projection counter over the matches
+    with both depths (``counts[:,4] / counts[:,3]``).  A summary whose threshold was off is ``None``.
+
+    Returns ``{'precision': float64 [P] or None, 'mean_precision': float or None, 'reproj_precision':
+    float64 [P] or None, 'mean_reproj_precision': float or None, 'n_pairs': scored pairs,
+    'n_not_scored': int, 'n_matches': matches of the scored pairs, 'n_both_depths': int}``; a mean over
+    no scored pair is NaN."""
+    counts = result['counts'] if isinstance(result, dict) else result
+    counts = counts.cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    counts = counts.reshape(-1, 5).astype(np.int64)
+    scored = counts[:, 0] >= 0
+
+    def share(hit, of):
+        if scored.any() and (hit[scored] < 0).any():          # that threshold was off
+            return None, None
+        per_pair = np.full(counts.shape[0], np.nan)
+        some = scored & (of > 0)
+        per_pair[scored] = 0.0
+        per_pair[some] = hit[some] / of[some]
+        return per_pair, float(per_pair[scored].mean()) if scored.any() else float('nan')
+
+    precision, mean_precision = share(counts[:, 1], counts[:, 0])
+    reproj, mean_reproj = share(counts[:, 4], counts[:, 3])
+    return {'precision': precision, 'mean_precision': mean_precision, 'reproj_precision': reproj,
+            'mean_reproj_precision': mean_reproj, 'n_pairs': int(scored.sum()), 'n_not_scored': int((~scored).sum()),
+            'n_matches': int(counts[scored, 0].sum()), 'n_both_depths': int(counts[scored, 3].sum())}

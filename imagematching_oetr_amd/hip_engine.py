@@ -129,6 +129,12 @@ COVIS_MAX_SIDE = 8192      # OETR_COVIS_MAX_SIDE
 CROP_BATCH_ABI_VERSION = 1
 CROP_BATCH_EXPORTS = ('oetr_crop_batch_abi_version', 'oetr_crop_batch_capacity', 'oetr_overlap_crop_batch')
 
+# The match-scoring extension (include/oetr_match_score.h): likewise
+MATCH_SCORE_ABI_VERSION = 1
+MATCH_SCORE_EXPORTS = ('oetr_match_score_abi_version', 'oetr_match_score')
+MATCH_SCORE_PARAM_DOUBLES = 20   # OETR_MATCH_SCORE_PARAM_DOUBLES
+MATCH_SCORE_COUNTERS = 5         # OETR_MATCH_SCORE_COUNTERS
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -348,6 +354,15 @@ def load_library(path=None):
     lib.oetr_overlap_crop_batch.argtypes = [vp, i, i, i, i, vp, vp, i, i, i, vp, vp, sz, vp, vp]
     if lib.oetr_crop_batch_abi_version() != CROP_BATCH_ABI_VERSION:
         raise RuntimeError(f'{p}: crop-batch ABI version {lib.oetr_crop_batch_abi_version()} != {CROP_BATCH_ABI_VERSION}')
+    # include/oetr_match_score.h
+    lib.oetr_match_score_abi_version.restype = i
+    lib.oetr_match_score_abi_version.argtypes = []
+    lib.oetr_match_score.restype = i
+    # maps, n_maps, idx1, idx2, params, offsets, n_pairs, k1, k2, n_matches, epi_thr, sym_thr, px_thr, values, flags, counts, stream
+    lib.oetr_match_score.argtypes = [vp, i, vp, vp, vp, vp, i, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                     vp, vp, vp, vp]
+    if lib.oetr_match_score_abi_version() != MATCH_SCORE_ABI_VERSION:
+        raise RuntimeError(f'{p}: match-score ABI version {lib.oetr_match_score_abi_version()} != {MATCH_SCORE_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
