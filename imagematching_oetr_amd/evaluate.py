@@ -11,7 +11,8 @@ dataset emits) or is computed on the device from depth maps, intrinsics and pose
 (``covis.overlap_boxes_from_batch``).  ``evaluate_indexed`` scores the feature-bank route the same
 way: a pair list over an image set, the ground truth by index from a ``covis_set.DepthSet``.
 ``match_precision`` summarises ``match_score.score_matches``: the reference's ``validation_error``
-precision per pair, from one read of the counters.
+precision per pair, from one read of the counters.  ``keypoint_repeatability`` summarises
+``keypoint_score.score_keypoints`` the same way: the reference's repeatability per pair and threshold.
 """
 import numpy as np
 import torch
@@ -163,3 +164,32 @@ def match_precision(result):
     return {'precision': precision, 'mean_precision': mean_precision, 'reproj_precision': reproj,
             'mean_reproj_precision': mean_reproj, 'n_pairs': int(scored.sum()), 'n_not_scored': int((~scored).sum()),
             'n_matches': int(counts[scored, 0].sum()), 'n_both_depths': int(counts[scored, 3].sum())}
+
+
+def keypoint_repeatability(result):
+    """The reference's repeatability (``pose_evaluate``, ``dloc/evaluate/utils/evaluation.py:170-179``;
+    ``get_repeatability``, ``utils.py:214-236``) of a ``keypoint_score.score_keypoints`` result, from ONE
+    device read of its ``counts`` int32 ``[P,2,2+T]`` (a tensor or an array of that shape is taken as
+    well).  Per pair and threshold ``repeatability`` = ``(c12 / kept12 + c21 / kept21) / 2``: per
+    direction the kept keypoints with a keypoint of the other picture closer than the threshold over
+    the kept keypoints, a direction that kept nothing contributing 0 as in the reference.  Pairs that
+    were not vouched for (all counters -1) are EXCLUDED - NaN rows - and counted in ``n_not_scored``.
+
+    Returns ``{'repeatability': float64 [P,T], 'mean_repeatability': float64 [T] (NaN over no scored
+    pair), 'thresholds': the result's (None for a bare array), 'n_pairs': scored pairs, 'n_not_scored':
+    int, 'n_keypoints': keypoints of the scored pairs, both directions, 'n_kept': int}``."""
+    counts = result['counts'] if isinstance(result, dict) else result
+    thresholds = result.get('thresholds') if isinstance(result, dict) else None
+    counts = counts.cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if counts.ndim != 3 or counts.shape[1] != 2 or counts.shape[2] < 2:
+        raise ValueError(f'counts must be [P,2,2+T], got {counts.shape}')
+    counts = counts.astype(np.int64)
+    scored = counts[:, 0, 0] >= 0
+    kept = counts[:, :, 1:2]
+    share = np.where(kept > 0, counts[:, :, 2:] / np.maximum(kept, 1), 0.0)
+    per_pair = (share[:, 0] + share[:, 1]) / 2
+    per_pair[~scored] = np.nan
+    mean = per_pair[scored].mean(0) if scored.any() else np.full(counts.shape[2] - 2, np.nan)
+    return {'repeatability': per_pair, 'mean_repeatability': mean, 'thresholds': thresholds,
+            'n_pairs': int(scored.sum()), 'n_not_scored': int((~scored).sum()),
+            'n_keypoints': int(counts[scored, :, 0].sum()), 'n_kept': int(counts[scored, :, 1].sum())}

@@ -135,6 +135,12 @@ MATCH_SCORE_EXPORTS = ('oetr_match_score_abi_version', 'oetr_match_score')
 MATCH_SCORE_PARAM_DOUBLES = 20   # OETR_MATCH_SCORE_PARAM_DOUBLES
 MATCH_SCORE_COUNTERS = 5         # OETR_MATCH_SCORE_COUNTERS
 
+# The keypoint-repeatability extension (include/oetr_keypoint_score.h): likewise
+KEYPOINT_SCORE_ABI_VERSION = 1
+KEYPOINT_SCORE_EXPORTS = ('oetr_keypoint_score_abi_version', 'oetr_keypoint_repeatability')
+KEYPOINT_SCORE_MAX_THRESHOLDS = 8   # OETR_KEYPOINT_SCORE_MAX_THRESHOLDS
+KEYPOINT_SCORE_HEAD_COUNTERS = 2    # OETR_KEYPOINT_SCORE_HEAD_COUNTERS
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -363,6 +369,17 @@ def load_library(path=None):
                                      vp, vp, vp, vp]
     if lib.oetr_match_score_abi_version() != MATCH_SCORE_ABI_VERSION:
         raise RuntimeError(f'{p}: match-score ABI version {lib.oetr_match_score_abi_version()} != {MATCH_SCORE_ABI_VERSION}')
+    # include/oetr_keypoint_score.h
+    lib.oetr_keypoint_score_abi_version.restype = i
+    lib.oetr_keypoint_score_abi_version.argtypes = []
+    lib.oetr_keypoint_repeatability.restype = i
+    # maps, n_maps, keypoints, n_keypoints, kp_offsets, idx1, idx2, params, n_pairs, thresholds (host), n_thresholds, max_kp,
+    # counts, nearest, dist_sq, stream
+    lib.oetr_keypoint_repeatability.argtypes = [vp, i, vp, C.c_int64, vp, vp, vp, vp, i, C.POINTER(C.c_double), i, i,
+                                                vp, vp, vp, vp]
+    if lib.oetr_keypoint_score_abi_version() != KEYPOINT_SCORE_ABI_VERSION:
+        raise RuntimeError(f'{p}: keypoint-score ABI version {lib.oetr_keypoint_score_abi_version()} != '
+                           f'{KEYPOINT_SCORE_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
