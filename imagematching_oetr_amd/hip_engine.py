@@ -141,6 +141,12 @@ KEYPOINT_SCORE_EXPORTS = ('oetr_keypoint_score_abi_version', 'oetr_keypoint_repe
 KEYPOINT_SCORE_MAX_THRESHOLDS = 8   # OETR_KEYPOINT_SCORE_MAX_THRESHOLDS
 KEYPOINT_SCORE_HEAD_COUNTERS = 2    # OETR_KEYPOINT_SCORE_HEAD_COUNTERS
 
+# The match-assembly extension (include/oetr_match_assembly.h): likewise
+MATCH_ASSEMBLY_ABI_VERSION = 1
+MATCH_ASSEMBLY_EXPORTS = ('oetr_match_assembly_abi_version', 'oetr_match_assembly_workspace_bytes',
+                          'oetr_assemble_matches')
+MATCH_ASSEMBLY_COUNTERS = 4         # OETR_MATCH_ASSEMBLY_COUNTERS
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -380,6 +386,18 @@ def load_library(path=None):
     if lib.oetr_keypoint_score_abi_version() != KEYPOINT_SCORE_ABI_VERSION:
         raise RuntimeError(f'{p}: keypoint-score ABI version {lib.oetr_keypoint_score_abi_version()} != '
                            f'{KEYPOINT_SCORE_ABI_VERSION}')
+    # include/oetr_match_assembly.h
+    lib.oetr_match_assembly_abi_version.restype = i
+    lib.oetr_match_assembly_abi_version.argtypes = []
+    lib.oetr_match_assembly_workspace_bytes.restype = sz
+    lib.oetr_match_assembly_workspace_bytes.argtypes = [i]
+    lib.oetr_assemble_matches.restype = i
+    # info, scales, n_pairs, kp0, off0, n_kp0, kp1, off1, n_kp1, matches, match_bytes, conf, min_matches, workspace,
+    # workspace_bytes, origin0, origin1, index0, index1, k1, k2, mconf, offsets, counts, few, n_few, stream
+    lib.oetr_assemble_matches.argtypes = [vp, vp, i, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, i, vp, i, vp, sz] + [vp] * 12
+    if lib.oetr_match_assembly_abi_version() != MATCH_ASSEMBLY_ABI_VERSION:
+        raise RuntimeError(f'{p}: match-assembly ABI version {lib.oetr_match_assembly_abi_version()} != '
+                           f'{MATCH_ASSEMBLY_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
