@@ -17,6 +17,7 @@ import ctypes as C
 import torch
 
 from . import hip_engine
+from ._inputs import _pair_tensor
 from .hip_engine import COVIS_MAX_SIDE, COVIS_PARAM_DOUBLES, _check, _CovisMap, _stream
 
 # One image's float64 record, 45 values: pose [0:16], inverse(pose) [16:32], K [32:41], bbox [41:43], ratio [43:45]
@@ -116,17 +117,6 @@ class DepthSet:
         return self._table, self._cameras
 
 
-def _pair_tensor(depth_set, pair_index):
-    """``pair_index`` -> int32 ``[P,2]`` on the set's device (a device tensor is taken as it is)."""
-    dev = depth_set.device
-    if torch.is_tensor(pair_index) and pair_index.is_cuda:
-        if pair_index.dtype != torch.int32 or pair_index.dim() != 2 or pair_index.shape[1] != 2 or pair_index.device != dev:
-            raise ValueError(f'a device pair_index must be int32 [P,2] on {dev}')
-        return pair_index
-    host = torch.as_tensor(pair_index, dtype=torch.int32).reshape(-1, 2)
-    return host.pin_memory().to(dev, non_blocking=True) if host.numel() else host.to(dev)
-
-
 def pair_params(depth_set, idx1, idx2):
     """The parameter blocks of the pairs ``(idx1[p], idx2[p])``: float64 ``[P,40]`` in the layout of
     ``covis.covis_params`` (``include/oetr_covis.h``), gathered from the set's camera records and
@@ -205,7 +195,7 @@ def overlap_boxes_indexed(depth_set, pair_index, out=None):
     ``out['workspace']``)."""
     dev = depth_set.device
     with torch.cuda.device(dev):
-        pairs = _pair_tensor(depth_set, pair_index)
+        pairs = _pair_tensor(dev, pair_index, pin=True)
         if pairs.shape[0] == 0:
             return covis_boxes_indexed(torch.empty(0, dtype=torch.uint8, device=dev), 0, 0, pairs[:, 0].contiguous(),
                                        pairs[:, 1].contiguous(), torch.empty(0, COVIS_PARAM_DOUBLES, dtype=torch.float64, device=dev), out)

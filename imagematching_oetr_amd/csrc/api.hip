@@ -122,6 +122,12 @@ struct Packer {
 
 namespace oetr {
 int set_last_error(int status, const char* msg) { return fail((oetr_status)status, msg); }
+oetr_status entry_fail(const char* entry, oetr_status status, const std::string& msg) {
+  return fail(status, std::string(entry) + ": " + msg);
+}
+oetr_status entry_hip(const char* entry, hipError_t e, const char* what) {
+  return e == hipSuccess ? OETR_OK : entry_fail(entry, OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
 }  // namespace oetr
 
 enum KernelId { K_ENC_A, K_ENC_BA, K_ENC_BDEC, K_ENC_B, K_DECODER, K_HEAT_CONV,

@@ -61,22 +61,18 @@ __global__ __launch_bounds__(64 * BANK_WAVES) void k_bank_gather(const BankGathe
 
 namespace {
 
-oetr_status bank_fail(oetr_status st, const std::string& msg) {
-  return (oetr_status)set_last_error(st, msg.c_str());
-}
-
 // host-side validation of a gather's arguments (`who`: the entry point, for the message)
 oetr_status bank_check(const char* who, const float* bank1, int bank1_images, const int32_t* idx1,
                        const float* bank2, int bank2_images, const int32_t* idx2, int n_pairs, long L1,
                        long L2) {
   if (!bank1 || !bank2 || !idx1 || !idx2)
-    return bank_fail(OETR_ERR_BAD_ARG, std::string(who) + ": NULL bank / index pointer");
+    return entry_fail(who, OETR_ERR_BAD_ARG, "NULL bank / index pointer");
   if (n_pairs <= 0 || bank1_images <= 0 || bank2_images <= 0)
-    return bank_fail(OETR_ERR_BAD_ARG, std::string(who) + ": need n_pairs > 0 and bank images > 0");
+    return entry_fail(who, OETR_ERR_BAD_ARG, "need n_pairs > 0 and bank images > 0");
   if (L1 < 1 || L2 < 1 || L1 > OETR_MAX_TOKENS || L2 > OETR_MAX_TOKENS)
-    return bank_fail(OETR_ERR_BAD_SHAPE, std::string(who) + ": need 1 <= L <= " + std::to_string(OETR_MAX_TOKENS));
+    return entry_fail(who, OETR_ERR_BAD_SHAPE, "need 1 <= L <= " + std::to_string(OETR_MAX_TOKENS));
   if ((long)n_pairs * (L1 + L2) > (1L << 30) / C)      // (the bound of a workspace: 32-bit row counts stay safe)
-    return bank_fail(OETR_ERR_BAD_SHAPE, std::string(who) + ": more than 2^22 token rows");
+    return entry_fail(who, OETR_ERR_BAD_SHAPE, "more than 2^22 token rows");
   return OETR_OK;
 }
 
@@ -97,8 +93,8 @@ oetr_status launch_bank_gather(const float* bank1, int bank1_images, const int32
     p.flags = status_word;
     const dim3 grid((unsigned)((Lmax + wg_rows - 1) / wg_rows), (unsigned)(2 * p.n_pairs));
     hipLaunchKernelGGL(k_bank_gather, grid, dim3(64 * BANK_WAVES), 0, s, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bank_fail(OETR_ERR_HIP, std::string("k_bank_gather: ") + hipGetErrorString(e));
+    const hipError_t e = hipGetLastError();             // (under the kernel's name: both entries launch it from here)
+    if (e != hipSuccess) return entry_fail("k_bank_gather", OETR_ERR_HIP, hipGetErrorString(e));
   }
   return OETR_OK;
 }
@@ -116,7 +112,7 @@ oetr_status oetr_bank_gather(const float* bank1, int bank1_images, const int32_t
                              const float* bank2, int bank2_images, const int32_t* idx2,
                              int n_pairs, int L1, int L2, float* tokens1, float* tokens2,
                              uint32_t* status_word, void* stream) {
-  if (!tokens1 || !tokens2) return bank_fail(OETR_ERR_BAD_ARG, "oetr_bank_gather: NULL token buffer");
+  if (!tokens1 || !tokens2) return entry_fail("oetr_bank_gather", OETR_ERR_BAD_ARG, "NULL token buffer");
   if (oetr_status rc = bank_check("oetr_bank_gather", bank1, bank1_images, idx1, bank2, bank2_images, idx2,
                                   n_pairs, L1, L2))
     return rc;
@@ -130,14 +126,14 @@ oetr_status oetr_forward_bank(oetr_handle h, const float* bank1, int bank1_image
                               int img_w2, void* workspace, size_t workspace_bytes, float* box1, float* box2,
                               uint32_t* flag_slot, void* stream) {
   // everything oetr_forward_tokens would refuse is refused here, before the gather is enqueued
-  if (!h || !box1 || !box2) return bank_fail(OETR_ERR_BAD_ARG, "oetr_forward_bank: NULL handle / box output");
+  if (!h || !box1 || !box2) return entry_fail("oetr_forward_bank", OETR_ERR_BAD_ARG, "NULL handle / box output");
   if (hf1 <= 0 || wf1 <= 0 || hf2 <= 0 || wf2 <= 0)
-    return bank_fail(OETR_ERR_BAD_SHAPE, "oetr_forward_bank: empty token grid");
+    return entry_fail("oetr_forward_bank", OETR_ERR_BAD_SHAPE, "empty token grid");
   if (oetr_status rc = bank_check("oetr_forward_bank", bank1, bank1_images, idx1, bank2, bank2_images, idx2,
                                   n_pairs, (long)hf1 * wf1, (long)hf2 * wf2))
     return rc;
   if (img_h1 < hf1 || img_h2 < hf2 || img_w1 <= 0 || img_w2 <= 0)
-    return bank_fail(OETR_ERR_BAD_SHAPE, "oetr_forward_bank: image size smaller than the token grid");
+    return entry_fail("oetr_forward_bank", OETR_ERR_BAD_SHAPE, "image size smaller than the token grid");
   float *tokens1, *tokens2, *pos1, *pos2;
   if (oetr_status rc = oetr_token_buffers(h, n_pairs, hf1, wf1, hf2, wf2, workspace, workspace_bytes, &tokens1,
                                           &tokens2, &pos1, &pos2))

@@ -4,7 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <type_traits>
+
+#include "../../include/oetr_hip.h"
 
 namespace oetr {
 
@@ -1095,6 +1098,13 @@ typedef WStream2T<GM_SPLIT> WStream2;
 // ------------------------------------------------------------------ host
 // sets the calling thread's oetr_last_error() text; returns `status` (api.hip)
 int set_last_error(int status, const char* msg);
+// The refusal of the entry point `entry`: sets the text "<entry>: <msg>", returns `status` (api.hip) ...
+oetr_status entry_fail(const char* entry, oetr_status status, const std::string& msg);
+// ... and the outcome of a HIP call or launch `what` made by it: OETR_OK, or OETR_ERR_HIP "<entry>: <what>: <HIP's text>"
+oetr_status entry_hip(const char* entry, hipError_t e, const char* what);
+// p[0 .. n) = 0 on stream s, by the library's one clearing kernel k_clear_i32 (match_score.hip, which says why a kernel);
+// 0 <= n <= INT32_MAX.  Returns the launch's hipGetLastError().
+hipError_t clear_i32(int32_t* p, int64_t n, hipStream_t s);
 // Repacked weights of one encoder layer (device pointers).
 struct EncLayerDev {
   const f32x4 *wq, *wk, *wv, *wmerge, *w1, *w2;  // fragment-packed (f32 mode: values;

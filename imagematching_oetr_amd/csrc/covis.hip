@@ -23,6 +23,7 @@
 
 #include "../../include/oetr_covis_set.h"
 #include "common.h"
+#include "depth_pose.h"
 
 namespace oetr {
 
@@ -146,20 +147,13 @@ __global__ __launch_bounds__(COVIS_THREADS) void k_covis_warp(const float* __res
               mask2 ? mask2 + map : nullptr);
 }
 
-// A table row the call may dereference: a pointer, sides within 1..SIDE, no more pixels than the caller vouched for.
-__device__ __forceinline__ bool covis_map_usable(const oetr_covis_map& m, int max_pixels) {
-  return m.depth != nullptr && m.H >= 1 && m.H <= SIDE && m.W >= 1 && m.W <= SIDE && m.H * m.W <= max_pixels;
-}
-
-// Both rows of pair `pair`, or false when the pair must not be dereferenced (include/oetr_covis_set.h).
+// Both rows of pair `pair`, or false when the pair must not be dereferenced (include/oetr_covis_set.h): depth_pose.h's
+// test, with no more pixels in a map than the caller vouched for (asked after the sides: H * W <= SIDE * SIDE).
 __device__ __forceinline__ bool covis_pair_maps(const oetr_covis_map* __restrict__ maps, int n_maps,
                                                 const int32_t* __restrict__ idx1, const int32_t* __restrict__ idx2,
                                                 int pair, int max_pixels, oetr_covis_map& a, oetr_covis_map& b) {
-  const int i1 = idx1[pair], i2 = idx2[pair];
-  if (i1 < 0 || i1 >= n_maps || i2 < 0 || i2 >= n_maps) return false;
-  a = maps[i1];
-  b = maps[i2];
-  return covis_map_usable(a, max_pixels) && covis_map_usable(b, max_pixels);
+  return pair_maps(maps, n_maps, idx1, idx2, pair, a, b,
+                   [=](const oetr_covis_map& m) { return map_usable(m) && m.H * m.W <= max_pixels; });
 }
 
 // grid: x = blocks of COVIS_PIX pixels up to max_pixels, y = pair.  The indices and the two table rows are
@@ -271,15 +265,6 @@ __global__ __launch_bounds__(SELECT_THREADS) void k_covis_select(const float* __
 
 namespace {
 
-oetr_status covis_fail(oetr_status st, const std::string& msg, const char* entry = "oetr_covis_boxes") {
-  return (oetr_status)set_last_error(st, (std::string(entry) + ": " + msg).c_str());
-}
-
-oetr_status covis_hip(hipError_t e, const char* what, const char* entry = "oetr_covis_boxes") {
-  return e == hipSuccess ? OETR_OK
-                         : covis_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), entry);
-}
-
 constexpr int COVIS_MAX_GRID_Y = 65535;                           // the grid's y extent: more pairs, more launches
 
 }  // namespace
@@ -298,24 +283,25 @@ size_t oetr_covis_workspace_bytes(int n_pairs) {
 oetr_status oetr_covis_boxes(const float* depth1, const float* depth2, const double* params, int n_pairs,
                              int H, int W, void* workspace, size_t workspace_bytes, float* box1, float* box2,
                              uint8_t* valid, int32_t* count, uint8_t* mask1, uint8_t* mask2, void* stream) {
-  if (!depth1 || !depth2 || !params) return covis_fail(OETR_ERR_BAD_ARG, "NULL depth / parameter pointer");
-  if (!box1 || !box2 || !valid) return covis_fail(OETR_ERR_BAD_ARG, "NULL box / valid output");
+  const char* me = "oetr_covis_boxes";
+  if (!depth1 || !depth2 || !params) return entry_fail(me, OETR_ERR_BAD_ARG, "NULL depth / parameter pointer");
+  if (!box1 || !box2 || !valid) return entry_fail(me, OETR_ERR_BAD_ARG, "NULL box / valid output");
   if ((mask1 == nullptr) != (mask2 == nullptr))
-    return covis_fail(OETR_ERR_BAD_ARG, "mask1 and mask2 must both be NULL or both be set");
-  if (n_pairs <= 0) return covis_fail(OETR_ERR_BAD_ARG, "need n_pairs > 0");
+    return entry_fail(me, OETR_ERR_BAD_ARG, "mask1 and mask2 must both be NULL or both be set");
+  if (n_pairs <= 0) return entry_fail(me, OETR_ERR_BAD_ARG, "need n_pairs > 0");
   if (H < 1 || W < 1 || H > SIDE || W > SIDE)
-    return covis_fail(OETR_ERR_BAD_SHAPE, "need 1 <= H, W <= " + std::to_string(SIDE));
+    return entry_fail(me, OETR_ERR_BAD_SHAPE, "need 1 <= H, W <= " + std::to_string(SIDE));
   const size_t need = oetr_covis_workspace_bytes(n_pairs);
   if (!workspace || workspace_bytes < need)
-    return covis_fail(OETR_ERR_BAD_ARG, "workspace NULL or smaller than oetr_covis_workspace_bytes(n_pairs) = " +
+    return entry_fail(me, OETR_ERR_BAD_ARG, "workspace NULL or smaller than oetr_covis_workspace_bytes(n_pairs) = " +
                                             std::to_string(need));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n_pix = (size_t)H * W;
   int* acc = static_cast<int*>(workspace);
-  if (oetr_status rc = covis_hip(hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)")) return rc;
+  if (oetr_status rc = entry_hip(me, hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)")) return rc;
   if (mask1) {
-    if (oetr_status rc = covis_hip(hipMemsetAsync(mask1, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask1)")) return rc;
-    if (oetr_status rc = covis_hip(hipMemsetAsync(mask2, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask2)")) return rc;
+    if (oetr_status rc = entry_hip(me, hipMemsetAsync(mask1, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask1)")) return rc;
+    if (oetr_status rc = entry_hip(me, hipMemsetAsync(mask2, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask2)")) return rc;
   }
   constexpr int max_pairs = COVIS_MAX_GRID_Y;
   const unsigned blocks = (unsigned)((n_pix + COVIS_PIX - 1) / COVIS_PIX);
@@ -325,11 +311,11 @@ oetr_status oetr_covis_boxes(const float* depth1, const float* depth2, const dou
     hipLaunchKernelGGL(k_covis_warp, dim3(blocks, (unsigned)n), dim3(COVIS_THREADS), 0, s, depth1 + off,
                        depth2 + off, params + (size_t)p0 * OETR_COVIS_PARAM_DOUBLES, H, W,
                        acc + (size_t)p0 * COVIS_ACC, mask1 ? mask1 + off : nullptr, mask2 ? mask2 + off : nullptr);
-    if (oetr_status rc = covis_hip(hipGetLastError(), "k_covis_warp")) return rc;
+    if (oetr_status rc = entry_hip(me, hipGetLastError(), "k_covis_warp")) return rc;
   }
   hipLaunchKernelGGL(k_covis_finish, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, acc, n_pairs, box1,
                      box2, valid, count);
-  return covis_hip(hipGetLastError(), "k_covis_finish");
+  return entry_hip(me, hipGetLastError(), "k_covis_finish");
 }
 
 int oetr_covis_set_abi_version(void) { return OETR_COVIS_SET_ABI_VERSION; }
@@ -341,18 +327,18 @@ oetr_status oetr_covis_boxes_indexed(const oetr_covis_map* maps, int n_maps, con
                                      void* workspace, size_t workspace_bytes, float* box1, float* box2,
                                      uint8_t* valid, int32_t* count, void* stream) {
   const char* me = "oetr_covis_boxes_indexed";
-  if (!maps || !idx1 || !idx2 || !params) return covis_fail(OETR_ERR_BAD_ARG, "NULL map table / index / parameter pointer", me);
-  if (!box1 || !box2 || !valid) return covis_fail(OETR_ERR_BAD_ARG, "NULL box / valid output", me);
-  if (n_maps <= 0 || n_pairs <= 0) return covis_fail(OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0", me);
+  if (!maps || !idx1 || !idx2 || !params) return entry_fail(me, OETR_ERR_BAD_ARG, "NULL map table / index / parameter pointer");
+  if (!box1 || !box2 || !valid) return entry_fail(me, OETR_ERR_BAD_ARG, "NULL box / valid output");
+  if (n_maps <= 0 || n_pairs <= 0) return entry_fail(me, OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0");
   if (max_pixels < 1 || max_pixels > (int64_t)SIDE * SIDE)
-    return covis_fail(OETR_ERR_BAD_SHAPE, "need 1 <= max_pixels <= " + std::to_string((int64_t)SIDE * SIDE), me);
+    return entry_fail(me, OETR_ERR_BAD_SHAPE, "need 1 <= max_pixels <= " + std::to_string((int64_t)SIDE * SIDE));
   const size_t need = oetr_covis_set_workspace_bytes(n_pairs);
   if (!workspace || workspace_bytes < need)
-    return covis_fail(OETR_ERR_BAD_ARG, "workspace NULL or smaller than oetr_covis_set_workspace_bytes(n_pairs) = " +
-                                            std::to_string(need), me);
+    return entry_fail(me, OETR_ERR_BAD_ARG, "workspace NULL or smaller than oetr_covis_set_workspace_bytes(n_pairs) = " +
+                                            std::to_string(need));
   hipStream_t s = static_cast<hipStream_t>(stream);
   int* acc = static_cast<int*>(workspace);
-  if (oetr_status rc = covis_hip(hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)", me)) return rc;
+  if (oetr_status rc = entry_hip(me, hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)")) return rc;
   const int max_pix = (int)max_pixels;
   const unsigned blocks = (unsigned)((max_pix + COVIS_PIX - 1) / COVIS_PIX);
   for (int p0 = 0; p0 < n_pairs; p0 += COVIS_MAX_GRID_Y) {
@@ -360,11 +346,11 @@ oetr_status oetr_covis_boxes_indexed(const oetr_covis_map* maps, int n_maps, con
     hipLaunchKernelGGL(k_covis_warp_indexed, dim3(blocks, (unsigned)n), dim3(COVIS_THREADS), 0, s, maps, n_maps,
                        idx1 + p0, idx2 + p0, params + (size_t)p0 * OETR_COVIS_PARAM_DOUBLES, max_pix,
                        acc + (size_t)p0 * COVIS_ACC);
-    if (oetr_status rc = covis_hip(hipGetLastError(), "k_covis_warp_indexed", me)) return rc;
+    if (oetr_status rc = entry_hip(me, hipGetLastError(), "k_covis_warp_indexed")) return rc;
   }
   hipLaunchKernelGGL(k_covis_finish_indexed, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, maps, n_maps,
                      idx1, idx2, max_pix, acc, n_pairs, box1, box2, valid, count);
-  return covis_hip(hipGetLastError(), "k_covis_finish_indexed", me);
+  return entry_hip(me, hipGetLastError(), "k_covis_finish_indexed");
 }
 
 oetr_status oetr_covis_select(const float* box1, const float* box2, const uint8_t* valid, int n_pairs,
@@ -372,13 +358,13 @@ oetr_status oetr_covis_select(const float* box1, const float* box2, const uint8_
                               void* workspace, size_t workspace_bytes, void* stream) {
   const char* me = "oetr_covis_select";
   (void)workspace; (void)workspace_bytes;                         // reserved (include/oetr_covis_set.h)
-  if (!box1 || !box2 || !valid) return covis_fail(OETR_ERR_BAD_ARG, "NULL box / valid input", me);
-  if (!kept || !n_kept) return covis_fail(OETR_ERR_BAD_ARG, "NULL kept / n_kept output", me);
-  if (n_pairs <= 0) return covis_fail(OETR_ERR_BAD_ARG, "need n_pairs > 0", me);
-  if (std::isnan(min_scale_diff)) return covis_fail(OETR_ERR_BAD_ARG, "min_scale_diff is NaN", me);
+  if (!box1 || !box2 || !valid) return entry_fail(me, OETR_ERR_BAD_ARG, "NULL box / valid input");
+  if (!kept || !n_kept) return entry_fail(me, OETR_ERR_BAD_ARG, "NULL kept / n_kept output");
+  if (n_pairs <= 0) return entry_fail(me, OETR_ERR_BAD_ARG, "need n_pairs > 0");
+  if (std::isnan(min_scale_diff)) return entry_fail(me, OETR_ERR_BAD_ARG, "min_scale_diff is NaN");
   hipLaunchKernelGGL(k_covis_select, dim3(1), dim3(SELECT_THREADS), 0, static_cast<hipStream_t>(stream), box1, box2,
                      valid, n_pairs, min_scale_diff, limit, kept, n_kept, scale_diff);
-  return covis_hip(hipGetLastError(), "k_covis_select", me);
+  return entry_hip(me, hipGetLastError(), "k_covis_select");
 }
 
 }  // extern "C"

@@ -7,11 +7,11 @@
 // on blockIdx alone: wave-uniform (scalar) loads.  The thread projects its keypoint itself - one depth pixel, three
 // float64 divisions, tests/keypoint_score_oracle.py::project LITERALLY: float64, every operation rounded on its own
 // in the order and with the parentheses written there (no contraction into FMAs) - so there is no buffer of projected
-// points.  The projection is the arithmetic of match_row in match_score.hip, RESTATED here (a dozen lines per
-// direction) rather than shared through a header: oetr_match_score's results are pinned bit for bit and its code
-// stays as it is.  The target picture's keypoints go through LDS in tiles of 256, widened to float64 once; in the
-// inner loop every lane reads the same LDS address (a broadcast: no bank conflict), and the running minimum is
-// taken with a strict "<" in ascending index order: the lowest index wins a tie, a NaN never wins.
+// points.  The depth read and the projection are depth_pose.h's, the one copy match_row of match_score.hip runs
+// too: a keypoint scored through either entry gives the same bits.  The target picture's keypoints go through LDS
+// in tiles of 256, widened to float64 once; in the inner loop every lane reads the same LDS address (a broadcast: no
+// bank conflict), and the running minimum is taken with a strict "<" in ascending index order: the lowest index wins
+// a tie, a NaN never wins.
 // A workgroup in which no row is kept skips the loop.
 //
 // Nothing is dereferenced on the strength of device data alone: the map indices are tested against n_maps, the
@@ -20,13 +20,14 @@
 //
 // Counters: one ballot and one popcount per wave for the kept rows and for each threshold, one atomicAdd per
 // non-zero count from the wave's first lane.  Integer atomics commute: the counters do not depend on arrival order.
-// k_keypoint_clear zeroes the counters before, k_keypoint_finish (one thread per pair and direction) afterwards
-// writes the source picture's keypoint count, or -1 throughout for a pair that is not vouched for.
+// clear_i32 (match_score.hip's k_clear_i32) zeroes the counters before, k_keypoint_finish (one thread per pair and
+// direction) afterwards writes the source picture's keypoint count, or -1 throughout for a pair that is not vouched for.
 #include <cmath>
 #include <string>
 
 #include "../../include/oetr_keypoint_score.h"
 #include "common.h"
+#include "depth_pose.h"
 
 namespace oetr {
 
@@ -35,15 +36,10 @@ constexpr int KP_TARGET_TILE = 256;                                 // target ke
 constexpr int KP_PARAMS = OETR_MATCH_SCORE_PARAM_DOUBLES;
 constexpr int KP_MAX_THR = OETR_KEYPOINT_SCORE_MAX_THRESHOLDS;
 constexpr int KP_HEAD = OETR_KEYPOINT_SCORE_HEAD_COUNTERS;
-constexpr int KP_SIDE = OETR_COVIS_MAX_SIDE;
 
 struct KpThresholds {
   double th[KP_MAX_THR];
 };
-
-__device__ __forceinline__ bool keypoint_map_usable(const oetr_covis_map& m) {
-  return m.depth != nullptr && m.H >= 1 && m.H <= KP_SIDE && m.W >= 1 && m.W <= KP_SIDE;
-}
 
 // The keypoint rows [first, first + count) of picture k, or false when they are not vouched for: every row then lies
 // in [0, n_keypoints) and count in [0, max_kp].  k is in [0, n_maps): reads kp_offsets[k], kp_offsets[k + 1].
@@ -68,58 +64,10 @@ __device__ __forceinline__ bool keypoint_pair(const oetr_covis_map* __restrict__
                                               const int32_t* __restrict__ idx1, const int32_t* __restrict__ idx2,
                                               int p, KpPair& out) {
   const int i1 = idx1[p], i2 = idx2[p];
-  if (i1 < 0 || i1 >= n_maps || i2 < 0 || i2 >= n_maps) return false;
-  out.m1 = maps[i1];
-  out.m2 = maps[i2];
-  if (!keypoint_map_usable(out.m1) || !keypoint_map_usable(out.m2)) return false;
+  if (!pair_maps(maps, n_maps, idx1, idx2, p, out.m1, out.m2)) return false;          // i1, i2 in [0, n_maps)
   const bool rows1 = keypoint_rows(kp_offsets, i1, n_keypoints, max_kp, out.first1, out.count1);
   const bool rows2 = keypoint_rows(kp_offsets, i2, n_keypoints, max_kp, out.first2, out.count2);
   return rows1 && rows2;
-}
-
-// Depth at (rint(v), rint(u)), half to even, 0 outside the map (match_depth_at of match_score.hip, restated).
-__device__ __forceinline__ double keypoint_depth_at(const oetr_covis_map& m, double u, double v) {
-#pragma clang fp contract(off)
-  const double c = rint(u), r = rint(v);
-  if (!(c >= 0.0 && c < (double)m.W && r >= 0.0 && r < (double)m.H)) return 0.0;
-  return (double)m.depth[(size_t)(int)r * (size_t)m.W + (size_t)(int)c];
-}
-
-// tests/keypoint_score_oracle.py::project, reverse=False: a keypoint of picture 1 in picture 2.
-__device__ __forceinline__ void keypoint_project12(const double* __restrict__ P, double u, double v, double d,
-                                                   double& pu, double& pv) {
-#pragma clang fp contract(off)
-  const double fx1 = P[0], fy1 = P[1], cx1 = P[2], cy1 = P[3], fx2 = P[4], fy2 = P[5], cx2 = P[6], cy2 = P[7];
-  const double R00 = P[8], R01 = P[9], R02 = P[10], R10 = P[11], R11 = P[12], R12 = P[13], R20 = P[14],
-               R21 = P[15], R22 = P[16];
-  const double t0 = P[17], t1 = P[18], t2 = P[19];
-  const double x1 = (u - cx1) / fx1, y1 = (v - cy1) / fy1;
-  const double X1 = x1 * d, Y1 = y1 * d;
-  const double p0 = ((R00 * X1 + R01 * Y1) + R02 * d) + t0;
-  const double p1 = ((R10 * X1 + R11 * Y1) + R12 * d) + t1;
-  const double p2 = ((R20 * X1 + R21 * Y1) + R22 * d) + t2;
-  pu = fx2 * (p0 / p2) + cx2;
-  pv = fy2 * (p1 / p2) + cy2;
-}
-
-// ... reverse=True: a keypoint of picture 2 in picture 1, under R^T and R^T t.
-__device__ __forceinline__ void keypoint_project21(const double* __restrict__ P, double u, double v, double d,
-                                                   double& pu, double& pv) {
-#pragma clang fp contract(off)
-  const double fx1 = P[0], fy1 = P[1], cx1 = P[2], cy1 = P[3], fx2 = P[4], fy2 = P[5], cx2 = P[6], cy2 = P[7];
-  const double R00 = P[8], R01 = P[9], R02 = P[10], R10 = P[11], R11 = P[12], R12 = P[13], R20 = P[14],
-               R21 = P[15], R22 = P[16];
-  const double t0 = P[17], t1 = P[18], t2 = P[19];
-  const double x2 = (u - cx2) / fx2, y2 = (v - cy2) / fy2;
-  const double m0 = (R00 * t0 + R10 * t1) + R20 * t2;
-  const double m1 = (R01 * t0 + R11 * t1) + R21 * t2;
-  const double m2 = (R02 * t0 + R12 * t1) + R22 * t2;
-  const double X2 = x2 * d, Y2 = y2 * d;
-  const double q0 = ((R00 * X2 + R10 * Y2) + R20 * d) - m0;
-  const double q1 = ((R01 * X2 + R11 * Y2) + R21 * d) - m1;
-  const double q2 = ((R02 * X2 + R12 * Y2) + R22 * d) - m2;
-  pu = fx1 * (q0 / q2) + cx1;
-  pv = fy1 * (q1 / q2) + cy1;
 }
 
 __global__ __launch_bounds__(KP_THREADS) void k_keypoint_nearest(
@@ -159,8 +107,8 @@ __global__ __launch_bounds__(KP_THREADS) void k_keypoint_nearest(
   if (active) {
     const float2 k = keypoints[(size_t)first_src + (size_t)a];      // first_src + a < first_src + n_src <= n_keypoints
     const double u = (double)k.x, v = (double)k.y;
-    const double d = keypoint_depth_at(src, u, v);
-    if (side) keypoint_project21(P, u, v, d, pu, pv); else keypoint_project12(P, u, v, d, pu, pv);
+    const double d = depth_at(src, u, v);
+    if (side) project21(P, u, v, d, pu, pv); else project12(P, u, v, d, pu, pv);
     kept = d != 0.0 && pu < (double)dst.W && pv < (double)dst.H;    // the reference's test: no lower bound; NaN fails
   }
 
@@ -208,12 +156,6 @@ __global__ __launch_bounds__(KP_THREADS) void k_keypoint_nearest(
   }
 }
 
-// counts = 0, as a kernel of the library's own (the note on hipMemsetAsync in match_score.hip)
-__global__ void k_keypoint_clear(int32_t* __restrict__ counts, int n) {
-  const unsigned at = blockIdx.x * blockDim.x + threadIdx.x;
-  if (at < (unsigned)n) counts[at] = 0;
-}
-
 // one thread per pair and direction; the vouching test k_keypoint_nearest made, made again
 __global__ void k_keypoint_finish(const oetr_covis_map* __restrict__ maps, int n_maps, int n_keypoints,
                                   const int32_t* __restrict__ kp_offsets, const int32_t* __restrict__ idx1,
@@ -233,13 +175,7 @@ __global__ void k_keypoint_finish(const oetr_covis_map* __restrict__ maps, int n
 
 namespace {
 
-oetr_status keypoint_fail(oetr_status st, const std::string& msg) {
-  return (oetr_status)set_last_error(st, ("oetr_keypoint_repeatability: " + msg).c_str());
-}
-
-oetr_status keypoint_hip(hipError_t e, const char* what) {
-  return e == hipSuccess ? OETR_OK : keypoint_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
+constexpr const char* ME = "oetr_keypoint_repeatability";
 
 }  // namespace
 }  // namespace oetr
@@ -258,39 +194,37 @@ oetr_status oetr_keypoint_repeatability(const oetr_covis_map* maps, int n_maps, 
                                         const double* thresholds, int n_thresholds, int max_kp, int32_t* counts,
                                         int32_t* nearest, double* dist_sq, void* stream) {
   if (!maps || !kp_offsets || !idx1 || !idx2 || !params)
-    return keypoint_fail(OETR_ERR_BAD_ARG, "NULL map table / offsets / index / parameter pointer");
-  if (!counts) return keypoint_fail(OETR_ERR_BAD_ARG, "NULL counts output");
-  if (n_maps <= 0 || n_pairs <= 0) return keypoint_fail(OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0");
-  if (n_keypoints < 0 || max_kp < 0) return keypoint_fail(OETR_ERR_BAD_ARG, "need n_keypoints >= 0 and max_kp >= 0");
-  if (n_keypoints != 0 && !keypoints) return keypoint_fail(OETR_ERR_BAD_ARG, "NULL keypoint pointer");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL map table / offsets / index / parameter pointer");
+  if (!counts) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL counts output");
+  if (n_maps <= 0 || n_pairs <= 0) return entry_fail(ME, OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0");
+  if (n_keypoints < 0 || max_kp < 0) return entry_fail(ME, OETR_ERR_BAD_ARG, "need n_keypoints >= 0 and max_kp >= 0");
+  if (n_keypoints != 0 && !keypoints) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL keypoint pointer");
   if (n_thresholds < 0 || n_thresholds > KP_MAX_THR)
-    return keypoint_fail(OETR_ERR_BAD_ARG, "need 0 <= n_thresholds <= " + std::to_string(KP_MAX_THR));
-  if (n_thresholds != 0 && !thresholds) return keypoint_fail(OETR_ERR_BAD_ARG, "NULL thresholds");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "need 0 <= n_thresholds <= " + std::to_string(KP_MAX_THR));
+  if (n_thresholds != 0 && !thresholds) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL thresholds");
   if (n_keypoints > (int64_t)INT32_MAX)
-    return keypoint_fail(OETR_ERR_BAD_SHAPE, "need n_keypoints <= " + std::to_string(INT32_MAX) + " (the offsets are int32)");
+    return entry_fail(ME, OETR_ERR_BAD_SHAPE, "need n_keypoints <= " + std::to_string(INT32_MAX) + " (the offsets are int32)");
   const int per_side = KP_HEAD + n_thresholds;
   const int64_t n_counters = 2 * (int64_t)n_pairs * per_side;
   const int64_t tiles = ((int64_t)max_kp + KP_THREADS - 1) / KP_THREADS;
   const int64_t blocks = 2 * (int64_t)n_pairs * tiles;
   if (n_counters > (int64_t)INT32_MAX || blocks > (int64_t)INT32_MAX)
-    return keypoint_fail(OETR_ERR_BAD_SHAPE, "more than " + std::to_string(INT32_MAX) + " counters or workgroups (2 * "
+    return entry_fail(ME, OETR_ERR_BAD_SHAPE, "more than " + std::to_string(INT32_MAX) + " counters or workgroups (2 * "
                          "n_pairs * ceil(max_kp / 256))");
   hipStream_t s = static_cast<hipStream_t>(stream);
   KpThresholds thr;
   for (int k = 0; k < KP_MAX_THR; ++k) thr.th[k] = k < n_thresholds ? thresholds[k] : 0.0;
-  // cleared by a kernel, not by a memset node: see oetr_match_score
-  hipLaunchKernelGGL(k_keypoint_clear, dim3((unsigned)((n_counters + 255) / 256)), dim3(256), 0, s, counts,
-                     (int)n_counters);
-  if (oetr_status rc = keypoint_hip(hipGetLastError(), "k_keypoint_clear")) return rc;
+  // cleared by a kernel, not by a memset node: see clear_i32 (match_score.hip)
+  if (oetr_status rc = entry_hip(ME, clear_i32(counts, n_counters, s), "k_clear_i32")) return rc;
   if (blocks > 0) {
     hipLaunchKernelGGL(k_keypoint_nearest, dim3((unsigned)blocks), dim3(KP_THREADS), 0, s, maps, n_maps,
                        reinterpret_cast<const float2*>(keypoints), (int)n_keypoints, kp_offsets, idx1, idx2, params,
                        (int)tiles, thr, n_thresholds, max_kp, counts, nearest, dist_sq);
-    if (oetr_status rc = keypoint_hip(hipGetLastError(), "k_keypoint_nearest")) return rc;
+    if (oetr_status rc = entry_hip(ME, hipGetLastError(), "k_keypoint_nearest")) return rc;
   }
   hipLaunchKernelGGL(k_keypoint_finish, dim3((unsigned)((2 * (int64_t)n_pairs + 255) / 256)), dim3(256), 0, s, maps,
                      n_maps, (int)n_keypoints, kp_offsets, idx1, idx2, n_pairs, n_thresholds, max_kp, counts);
-  return keypoint_hip(hipGetLastError(), "k_keypoint_finish");
+  return entry_hip(ME, hipGetLastError(), "k_keypoint_finish");
 }
 
 }  // extern "C"

@@ -264,13 +264,7 @@ __global__ __launch_bounds__(ASM_THREADS) void k_asm_emit(
 
 namespace {
 
-oetr_status asm_fail(oetr_status st, const std::string& msg) {
-  return (oetr_status)set_last_error(st, ("oetr_assemble_matches: " + msg).c_str());
-}
-
-oetr_status asm_hip(hipError_t e, const char* what) {
-  return e == hipSuccess ? OETR_OK : asm_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
+constexpr const char* ME = "oetr_assemble_matches";
 
 bool asm_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
@@ -283,13 +277,13 @@ oetr_status asm_launch(const oetr_crop_info* info, const double* scales, int n_p
   const M* m = static_cast<const M*>(matches);
   hipLaunchKernelGGL(k_asm_count<M>, dim3((unsigned)n_pairs), dim3(ASM_THREADS), 0, s, info, off0, n0, off1, n1, m,
                      kept_ws, counts);
-  if (oetr_status rc = asm_hip(hipGetLastError(), "k_asm_count")) return rc;
+  if (oetr_status rc = entry_hip(ME, hipGetLastError(), "k_asm_count")) return rc;
   hipLaunchKernelGGL(k_asm_scan, dim3(1), dim3(ASM_SCAN_THREADS), 0, s, kept_ws, counts, n_pairs, n0, min_matches,
                      offsets, few, n_few);
-  if (oetr_status rc = asm_hip(hipGetLastError(), "k_asm_scan")) return rc;
+  if (oetr_status rc = entry_hip(ME, hipGetLastError(), "k_asm_scan")) return rc;
   hipLaunchKernelGGL(k_asm_emit<M>, dim3((unsigned)n_pairs), dim3(ASM_THREADS), 0, s, info, scales, n_pairs, kp0, off0,
                      n0, kp1, off1, n1, m, conf, offsets, origin0, origin1, index0, index1, k1, k2, mconf);
-  return asm_hip(hipGetLastError(), "k_asm_emit");
+  return entry_hip(ME, hipGetLastError(), "k_asm_emit");
 }
 
 }  // namespace
@@ -315,30 +309,30 @@ oetr_status oetr_assemble_matches(const oetr_crop_info* info, const double* scal
                                   float* mconf, int32_t* offsets, int32_t* counts, int32_t* few, int32_t* n_few,
                                   void* stream) {
   if (!info || !scales || !off0 || !off1)
-    return asm_fail(OETR_ERR_BAD_ARG, "NULL geometry record / scales / off0 / off1 pointer");
-  if (!offsets || !counts) return asm_fail(OETR_ERR_BAD_ARG, "NULL offsets / counts output");
-  if (!workspace) return asm_fail(OETR_ERR_BAD_ARG, "NULL workspace");
-  if (n_pairs <= 0) return asm_fail(OETR_ERR_BAD_ARG, "need n_pairs > 0");
-  if (n_kp0 < 0 || n_kp1 < 0) return asm_fail(OETR_ERR_BAD_ARG, "need n_kp0 >= 0 and n_kp1 >= 0");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL geometry record / scales / off0 / off1 pointer");
+  if (!offsets || !counts) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL offsets / counts output");
+  if (!workspace) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL workspace");
+  if (n_pairs <= 0) return entry_fail(ME, OETR_ERR_BAD_ARG, "need n_pairs > 0");
+  if (n_kp0 < 0 || n_kp1 < 0) return entry_fail(ME, OETR_ERR_BAD_ARG, "need n_kp0 >= 0 and n_kp1 >= 0");
   if (match_bytes != 4 && match_bytes != 8)
-    return asm_fail(OETR_ERR_BAD_ARG, "match_bytes must be 4 (int32) or 8 (int64), got " + std::to_string(match_bytes));
-  if (min_matches < 0) return asm_fail(OETR_ERR_BAD_ARG, "need min_matches >= 0 (few = n_few = NULL: no selection)");
-  if ((few == nullptr) != (n_few == nullptr)) return asm_fail(OETR_ERR_BAD_ARG, "few and n_few go together");
-  if (n_kp0 != 0 && (!kp0 || !matches)) return asm_fail(OETR_ERR_BAD_ARG, "NULL kp0 / matches pointer");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "match_bytes must be 4 (int32) or 8 (int64), got " + std::to_string(match_bytes));
+  if (min_matches < 0) return entry_fail(ME, OETR_ERR_BAD_ARG, "need min_matches >= 0 (few = n_few = NULL: no selection)");
+  if ((few == nullptr) != (n_few == nullptr)) return entry_fail(ME, OETR_ERR_BAD_ARG, "few and n_few go together");
+  if (n_kp0 != 0 && (!kp0 || !matches)) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL kp0 / matches pointer");
   if (n_kp0 != 0 && (!origin0 || !index0 || !index1 || !k1 || !k2))
-    return asm_fail(OETR_ERR_BAD_ARG, "NULL origin0 / index0 / index1 / k1 / k2 output");
-  if (n_kp1 != 0 && (!kp1 || !origin1)) return asm_fail(OETR_ERR_BAD_ARG, "NULL kp1 / origin1 pointer");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL origin0 / index0 / index1 / k1 / k2 output");
+  if (n_kp1 != 0 && (!kp1 || !origin1)) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL kp1 / origin1 pointer");
   if (n_kp0 != 0 && (conf == nullptr) != (mconf == nullptr))
-    return asm_fail(OETR_ERR_BAD_ARG, "conf and mconf go together");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "conf and mconf go together");
   if (!asm_aligned(kp0, 8) || !asm_aligned(kp1, 8) || !asm_aligned(k1, 8) || !asm_aligned(k2, 8) ||
       !asm_aligned(origin0, 16) || !asm_aligned(origin1, 16) || !asm_aligned(matches, (uintptr_t)match_bytes))
-    return asm_fail(OETR_ERR_BAD_ARG, "keypoint rows must be 8-byte aligned, origin rows 16-byte, matches to their size");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "keypoint rows must be 8-byte aligned, origin rows 16-byte, matches to their size");
   if (n_pairs > INT32_MAX / ASM_COUNTERS)
-    return asm_fail(OETR_ERR_BAD_SHAPE, "need n_pairs <= " + std::to_string(INT32_MAX / ASM_COUNTERS));
+    return entry_fail(ME, OETR_ERR_BAD_SHAPE, "need n_pairs <= " + std::to_string(INT32_MAX / ASM_COUNTERS));
   if (n_kp0 > (int64_t)INT32_MAX || n_kp1 > (int64_t)INT32_MAX)
-    return asm_fail(OETR_ERR_BAD_SHAPE, "need n_kp0, n_kp1 <= " + std::to_string(INT32_MAX) + " (the offsets are int32)");
+    return entry_fail(ME, OETR_ERR_BAD_SHAPE, "need n_kp0, n_kp1 <= " + std::to_string(INT32_MAX) + " (the offsets are int32)");
   if (workspace_bytes < oetr_match_assembly_workspace_bytes(n_pairs))
-    return asm_fail(OETR_ERR_WORKSPACE, "workspace of " + std::to_string(workspace_bytes) + " bytes, need " +
+    return entry_fail(ME, OETR_ERR_WORKSPACE, "workspace of " + std::to_string(workspace_bytes) + " bytes, need " +
                                             std::to_string(oetr_match_assembly_workspace_bytes(n_pairs)));
   hipStream_t s = static_cast<hipStream_t>(stream);
   int32_t* kept_ws = static_cast<int32_t*>(workspace);

@@ -19,7 +19,7 @@
 //
 // Counters: a wave whose counted rows all belong to one pair takes one ballot and one popcount per flag and
 // issues one atomicAdd per non-zero counter; a wave that straddles lists falls back to per-lane atomicAdd.
-// Integer atomics commute: the counters do not depend on arrival order.  k_match_clear zeroes the counters before,
+// Integer atomics commute: the counters do not depend on arrival order.  k_clear_i32 zeroes the counters before,
 // k_match_finish (one thread per pair) afterwards writes the list length, -1 for a threshold that is off, and -1 throughout
 // for a pair that is not vouched for.
 #include <cmath>
@@ -27,37 +27,13 @@
 
 #include "../../include/oetr_match_score.h"
 #include "common.h"
+#include "depth_pose.h"
 
 namespace oetr {
 
 constexpr int MATCH_THREADS = 256;
 constexpr int MATCH_PARAMS = OETR_MATCH_SCORE_PARAM_DOUBLES;
 constexpr int MATCH_COUNTERS = OETR_MATCH_SCORE_COUNTERS;
-constexpr int MATCH_SIDE = OETR_COVIS_MAX_SIDE;
-
-__device__ __forceinline__ bool match_map_usable(const oetr_covis_map& m) {
-  return m.depth != nullptr && m.H >= 1 && m.H <= MATCH_SIDE && m.W >= 1 && m.W <= MATCH_SIDE;
-}
-
-// Both table rows of pair p, or false when the pair must not be dereferenced.
-__device__ __forceinline__ bool match_pair_maps(const oetr_covis_map* __restrict__ maps, int n_maps,
-                                                const int32_t* __restrict__ idx1, const int32_t* __restrict__ idx2,
-                                                int p, oetr_covis_map& a, oetr_covis_map& b) {
-  const int i1 = idx1[p], i2 = idx2[p];
-  if (i1 < 0 || i1 >= n_maps || i2 < 0 || i2 >= n_maps) return false;
-  a = maps[i1];
-  b = maps[i2];
-  return match_map_usable(a) && match_map_usable(b);
-}
-
-// Depth at (rint(v), rint(u)), half to even, 0 outside the map.  The range test is made in float64 on the rounded
-// coordinates: NaN and +-inf fail it, -0 passes; only then is anything converted to an integer.
-__device__ __forceinline__ double match_depth_at(const oetr_covis_map& m, double u, double v) {
-#pragma clang fp contract(off)
-  const double c = rint(u), r = rint(v);
-  if (!(c >= 0.0 && c < (double)m.W && r >= 0.0 && r < (double)m.H)) return 0.0;
-  return (double)m.depth[(size_t)(int)r * (size_t)m.W + (size_t)(int)c];
-}
 
 // The largest p in [0, n_pairs) with offsets[p] <= m, or -1: the number of such entries, less one (the offsets are
 // assumed non-decreasing).  Reads offsets[0 .. n_pairs-1] only.
@@ -102,21 +78,14 @@ __device__ __forceinline__ MatchRow match_row(const oetr_covis_map& ma, const oe
   out.epi = s2 * (1.0 / (a0 + a1) + 1.0 / (b0 + b1));
   out.sym = s2 * (1.0 / (a0 * a0 + a1 * a1) + 1.0 / (b0 * b0 + b1 * b1));
 
-  const double d1 = match_depth_at(ma, u1, v1), d2 = match_depth_at(mb, u2, v2);
-  const double X1 = x1 * d1, Y1 = y1 * d1;
-  const double p0 = ((R00 * X1 + R01 * Y1) + R02 * d1) + t0;
-  const double p1 = ((R10 * X1 + R11 * Y1) + R12 * d1) + t1;
-  const double p2 = ((R20 * X1 + R21 * Y1) + R22 * d1) + t2;
-  const double e0 = (fx2 * (p0 / p2) + cx2) - u2, e1 = (fy2 * (p1 / p2) + cy2) - v2;
+  // each keypoint under its depth in the other picture (depth_pose.h), against its partner
+  const double d1 = depth_at(ma, u1, v1), d2 = depth_at(mb, u2, v2);
+  double pu, pv;
+  project12(P, u1, v1, d1, pu, pv);
+  const double e0 = pu - u2, e1 = pv - v2;
   out.r12 = e0 * e0 + e1 * e1;
-  const double m0 = (R00 * t0 + R10 * t1) + R20 * t2;
-  const double m1 = (R01 * t0 + R11 * t1) + R21 * t2;
-  const double m2 = (R02 * t0 + R12 * t1) + R22 * t2;
-  const double X2 = x2 * d2, Y2 = y2 * d2;
-  const double q0 = ((R00 * X2 + R10 * Y2) + R20 * d2) - m0;
-  const double q1 = ((R01 * X2 + R11 * Y2) + R21 * d2) - m1;
-  const double q2 = ((R02 * X2 + R12 * Y2) + R22 * d2) - m2;
-  const double g0 = (fx1 * (q0 / q2) + cx1) - u1, g1 = (fy1 * (q1 / q2) + cy1) - v1;
+  project21(P, u2, v2, d2, pu, pv);
+  const double g0 = pu - u1, g1 = pv - v1;
   out.r21 = g0 * g0 + g1 * g1;
 
   const bool has1 = d1 != 0.0, has2 = d2 != 0.0;
@@ -170,12 +139,12 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_match_score(
   oetr_covis_map ma, mb;
   if (__ballot(active && p != p0) == 0ull) {
     // every active row of the wave is in list p0: indices, table rows and parameters by scalar loads
-    if (p0 >= 0 && match_pair_maps(maps, n_maps, idx1, idx2, p0, ma, mb) && active) {
+    if (p0 >= 0 && pair_maps(maps, n_maps, idx1, idx2, p0, ma, mb) && active) {
       r = match_row(ma, mb, params + (size_t)p0 * MATCH_PARAMS, (double)u1, (double)v1, (double)u2, (double)v2,
                     epi_thr, sym_thr, px_thr);
       counted = p0;
     }
-  } else if (p >= 0 && match_pair_maps(maps, n_maps, idx1, idx2, p, ma, mb)) {
+  } else if (p >= 0 && pair_maps(maps, n_maps, idx1, idx2, p, ma, mb)) {
     r = match_row(ma, mb, params + (size_t)p * MATCH_PARAMS, (double)u1, (double)v1, (double)u2, (double)v2, epi_thr,
                   sym_thr, px_thr);
     counted = p;
@@ -220,10 +189,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_match_score(
   }
 }
 
-// counts = 0, as a kernel of the library's own: see the note on hipMemsetAsync in oetr_match_score below
-__global__ void k_match_clear(int32_t* __restrict__ counts, int n) {
+// p[0 .. n) = 0, as a kernel of the library's own: see the note on hipMemsetAsync at clear_i32 below
+__global__ void k_clear_i32(int32_t* __restrict__ p, int n) {
   const unsigned at = blockIdx.x * blockDim.x + threadIdx.x;
-  if (at < (unsigned)n) counts[at] = 0;
+  if (at < (unsigned)n) p[at] = 0;
 }
 
 // one thread per pair; the vouching test k_match_score made, made again
@@ -236,7 +205,7 @@ __global__ void k_match_finish(const oetr_covis_map* __restrict__ maps, int n_ma
   const int p = (int)at;
   int32_t* c = counts + (size_t)p * MATCH_COUNTERS;
   oetr_covis_map a, b;
-  if (!match_pair_maps(maps, n_maps, idx1, idx2, p, a, b)) {
+  if (!pair_maps(maps, n_maps, idx1, idx2, p, a, b)) {
 #pragma unroll
     for (int k = 0; k < MATCH_COUNTERS; ++k) c[k] = -1;
     return;
@@ -249,15 +218,19 @@ __global__ void k_match_finish(const oetr_covis_map* __restrict__ maps, int n_ma
   if (px_thr != px_thr) c[4] = -1;
 }
 
+// The entries' counters are cleared by a kernel, not by hipMemsetAsync: captured into a HIP graph as a memset node
+// (280 bytes for 14 pairs), the clearing wrote a foreign 16-byte pattern over counts on the graph's SECOND replay,
+// after device copies had run between the replays (tests/test_gpu_match_score.py, the capture test; the runtime's
+// side of it was not examined).  A kernel node carries its arguments with it.  The kernel is launched from the file
+// that defines it (the build is not relocatable), so the other entries reach it through this function.
+hipError_t clear_i32(int32_t* p, int64_t n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_clear_i32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, (int)n);
+  return hipGetLastError();
+}
+
 namespace {
 
-oetr_status match_fail(oetr_status st, const std::string& msg) {
-  return (oetr_status)set_last_error(st, ("oetr_match_score: " + msg).c_str());
-}
-
-oetr_status match_hip(hipError_t e, const char* what) {
-  return e == hipSuccess ? OETR_OK : match_fail(OETR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
+constexpr const char* ME = "oetr_match_score";
 
 }  // namespace
 }  // namespace oetr
@@ -274,34 +247,29 @@ oetr_status oetr_match_score(const oetr_covis_map* maps, int n_maps, const int32
                              const float* k2, int64_t n_matches, double epi_thr, double sym_thr, double px_thr,
                              double* values, uint8_t* flags, int32_t* counts, void* stream) {
   if (!maps || !idx1 || !idx2 || !params || !offsets)
-    return match_fail(OETR_ERR_BAD_ARG, "NULL map table / index / parameter / offsets pointer");
-  if (!counts) return match_fail(OETR_ERR_BAD_ARG, "NULL counts output");
-  if (n_matches != 0 && (!k1 || !k2)) return match_fail(OETR_ERR_BAD_ARG, "NULL keypoint pointer");
-  if (n_matches != 0 && !flags) return match_fail(OETR_ERR_BAD_ARG, "NULL flags output");
-  if (n_maps <= 0 || n_pairs <= 0) return match_fail(OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0");
-  if (n_matches < 0) return match_fail(OETR_ERR_BAD_ARG, "need n_matches >= 0");
+    return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL map table / index / parameter / offsets pointer");
+  if (!counts) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL counts output");
+  if (n_matches != 0 && (!k1 || !k2)) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL keypoint pointer");
+  if (n_matches != 0 && !flags) return entry_fail(ME, OETR_ERR_BAD_ARG, "NULL flags output");
+  if (n_maps <= 0 || n_pairs <= 0) return entry_fail(ME, OETR_ERR_BAD_ARG, "need n_maps > 0 and n_pairs > 0");
+  if (n_matches < 0) return entry_fail(ME, OETR_ERR_BAD_ARG, "need n_matches >= 0");
   if (n_pairs > INT32_MAX / MATCH_COUNTERS)
-    return match_fail(OETR_ERR_BAD_SHAPE, "need n_pairs <= " + std::to_string(INT32_MAX / MATCH_COUNTERS));
+    return entry_fail(ME, OETR_ERR_BAD_SHAPE, "need n_pairs <= " + std::to_string(INT32_MAX / MATCH_COUNTERS));
   if (n_matches > (int64_t)INT32_MAX)
-    return match_fail(OETR_ERR_BAD_SHAPE, "need n_matches <= " + std::to_string(INT32_MAX) + " (the offsets are int32)");
+    return entry_fail(ME, OETR_ERR_BAD_SHAPE, "need n_matches <= " + std::to_string(INT32_MAX) + " (the offsets are int32)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int n = (int)n_matches;
-  // The counters are cleared by a kernel, not by hipMemsetAsync: captured into a HIP graph as a memset node (280
-  // bytes for 14 pairs), the clearing wrote a foreign 16-byte pattern over counts on the graph's SECOND replay, after
-  // device copies had run between the replays (tests/test_gpu_match_score.py, the capture test; the runtime's side
-  // of it was not examined).  A kernel node carries its arguments with it.
-  const int n_counters = n_pairs * MATCH_COUNTERS;                  // n_pairs <= INT32_MAX / 5, checked above
-  hipLaunchKernelGGL(k_match_clear, dim3((unsigned)((n_counters + 255) / 256)), dim3(256), 0, s, counts, n_counters);
-  if (oetr_status rc = match_hip(hipGetLastError(), "k_match_clear")) return rc;
+  // n_pairs <= INT32_MAX / 5, checked above
+  if (oetr_status rc = entry_hip(ME, clear_i32(counts, (int64_t)n_pairs * MATCH_COUNTERS, s), "k_clear_i32")) return rc;
   if (n > 0) {
     const unsigned blocks = (unsigned)(((int64_t)n + MATCH_THREADS - 1) / MATCH_THREADS);
     hipLaunchKernelGGL(k_match_score, dim3(blocks), dim3(MATCH_THREADS), 0, s, maps, n_maps, idx1, idx2, params,
                        offsets, n_pairs, k1, k2, n, epi_thr, sym_thr, px_thr, values, flags, counts);
-    if (oetr_status rc = match_hip(hipGetLastError(), "k_match_score")) return rc;
+    if (oetr_status rc = entry_hip(ME, hipGetLastError(), "k_match_score")) return rc;
   }
   hipLaunchKernelGGL(k_match_finish, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, maps, n_maps, idx1,
                      idx2, offsets, n_pairs, n, epi_thr, sym_thr, px_thr, counts);
-  return match_hip(hipGetLastError(), "k_match_finish");
+  return entry_hip(ME, hipGetLastError(), "k_match_finish");
 }
 
 }  // extern "C"

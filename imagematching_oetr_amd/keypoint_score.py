@@ -26,9 +26,10 @@ import numpy as np
 import torch
 
 from . import hip_engine
-from .hip_engine import (KEYPOINT_SCORE_HEAD_COUNTERS, KEYPOINT_SCORE_MAX_THRESHOLDS, MATCH_SCORE_PARAM_DOUBLES, _check,
-                         _stream)
-from .match_score import _is_host, _keypoints, _refuse_float64, _upload, match_params
+from ._inputs import (_is_host, _keypoints, _offsets_of, _pair_blocks, _pair_tensor, _refuse_float64,
+                      _refuse_host_inputs_in_capture, _upload)
+from .hip_engine import KEYPOINT_SCORE_HEAD_COUNTERS, KEYPOINT_SCORE_MAX_THRESHOLDS, _check, _stream
+from .match_score import match_params
 
 
 def _is_concatenated(keypoints):
@@ -92,32 +93,28 @@ def score_keypoints(depth_set, pair_index, keypoints, thresholds=(1, 2, 3, 5), n
                              'depth map of the picture of keypoints[k]')
         host_inputs.append('keypoints (a sequence: its offsets are uploaded)')
     with torch.cuda.device(dev):
-        if host_inputs and torch.cuda.is_current_stream_capturing():
-            raise ValueError(f'inside a graph capture every input must be a device tensor; on the host: {host_inputs}')
+        _refuse_host_inputs_in_capture(host_inputs)
         if concatenated:
             cat, kp_offsets, max_kp = keypoints
             if _is_host(cat) or _is_host(kp_offsets):
                 raise ValueError('keypoints=(cat, kp_offsets, max_kp): cat and kp_offsets must be device tensors')
             if cat.dtype != torch.float32:
                 raise ValueError(f'keypoints[0] must be float32, got {cat.dtype}')
-            cat = _keypoints('keypoints[0]', cat, dev)
+            cat = _keypoints('keypoints[0]', cat, dev, 'depth-map set')
             kp_offsets = _upload('keypoints[1]', kp_offsets, torch.int32, (n_maps + 1,), dev)
             max_kp = int(max_kp)
             if max_kp < 0:
                 raise ValueError(f'max_kp must be >= 0, got {max_kp}')
         else:
-            sets = [_keypoints(f'keypoints[{k}]', kp, dev) for k, kp in enumerate(keypoints)]
+            sets = [_keypoints(f'keypoints[{k}]', kp, dev, 'depth-map set') for k, kp in enumerate(keypoints)]
             lengths = [int(kp.shape[0]) for kp in sets]
             cat = torch.cat(sets) if sets else torch.zeros(0, 2, dtype=torch.float32, device=dev)
-            kp_offsets = torch.as_tensor(np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int32)).to(dev)
+            kp_offsets = _offsets_of(lengths, dev)
             max_kp = max(lengths, default=0)
         N = int(cat.shape[0])
         if N > 2 ** 31 - 1:
             raise ValueError('more than 2^31 - 1 keypoints in one call')
-        if _is_host(pair_index):
-            pair_index = torch.as_tensor(np.asarray(pair_index, dtype=np.int32).reshape(-1, 2)).to(dev)
-        if pair_index.dtype != torch.int32 or pair_index.dim() != 2 or pair_index.shape[1] != 2 or pair_index.device != dev:
-            raise ValueError(f'a device pair_index must be int32 [P,2] on {dev}')
+        pair_index = _pair_tensor(dev, pair_index)
         P = int(pair_index.shape[0])
         if out is None:
             out = {'counts': torch.zeros(P, 2, KEYPOINT_SCORE_HEAD_COUNTERS + T, dtype=torch.int32, device=dev)}
@@ -134,12 +131,7 @@ def score_keypoints(depth_set, pair_index, keypoints, thresholds=(1, 2, 3, 5), n
                 out['nearest'].fill_(-1)
                 out['dist_sq'].fill_(math.nan)
             return out
-        idx1, idx2 = pair_index[:, 0].contiguous(), pair_index[:, 1].contiguous()
-        table, _ = depth_set._commit()
-        if params is None:
-            params = match_params(depth_set, idx1, idx2)
-        else:
-            params = _upload('params', params, torch.float64, (P, MATCH_SCORE_PARAM_DOUBLES), dev)
+        idx1, idx2, table, params = _pair_blocks(depth_set, pair_index, params, match_params)
         lib = hip_engine.load_library()
         ptr = lambda t: t.data_ptr() if t.numel() else None
         thr = (ctypes.c_double * max(T, 1))(*thresholds)

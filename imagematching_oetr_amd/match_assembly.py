@@ -21,30 +21,16 @@ import numpy as np
 import torch
 
 from . import hip_engine
+from ._inputs import (_is_host, _keypoints, _offsets_of, _refuse_float64, _refuse_host_inputs_in_capture,
+                      _upload)
 from .crop_batch import OverlapCropBatch
 from .hip_engine import MATCH_ASSEMBLY_COUNTERS, _check, _CropInfo, _stream
-from .match_score import _is_host, _refuse_float64, _upload
 
 _INFO_BYTES = C.sizeof(_CropInfo)
 
 
 def _device_of(crops):
     return crops.info.device if isinstance(crops, OverlapCropBatch) else crops.device
-
-
-def _crop_keypoints(name, k, dev):
-    """``k`` -> contiguous float32 ``[K,2]`` on ``dev`` whose rows start on 8 bytes (the kernel moves a row as one
-    vector); float16 widened; a host array is uploaded (blocking); a view at an odd float is copied."""
-    if _is_host(k):
-        k = torch.as_tensor(np.asarray(k) if not torch.is_tensor(k) else k)
-    if k.dtype not in (torch.float32, torch.float16):
-        raise ValueError(f'{name} must be float32 or float16, got {k.dtype}')
-    if k.dim() != 2 or k.shape[1] != 2:
-        raise ValueError(f'{name} must be [K,2], got {tuple(k.shape)}')
-    if k.is_cuda and k.device != dev:
-        raise ValueError(f'{name} is on {k.device}, the geometry records on {dev}')
-    k = k.to(device=dev, dtype=torch.float32).contiguous()           # from the host: a blocking copy
-    return k.clone() if k.data_ptr() % 8 else k
 
 
 def _join(name, seq, dev):
@@ -54,10 +40,6 @@ def _join(name, seq, dev):
     if not parts:
         raise ValueError(f'{name}: an empty sequence')
     return torch.cat([t.to(dev) for t in parts]), [int(t.shape[0]) for t in parts]
-
-
-def _offsets_of(lengths, dev):
-    return torch.as_tensor(np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int32)).to(dev)
 
 
 @torch.no_grad()
@@ -122,8 +104,7 @@ def assemble_matches(crops, scales, kp0, kp1, matches, conf=None, offsets0=None,
         host_inputs += [n for n, seq in (('kp0', kp0), ('kp1', kp1), ('matches', matches), ('conf', conf))
                         if seq is not None and any(_is_host(t) for t in seq)]
     with torch.cuda.device(dev):
-        if host_inputs and torch.cuda.is_current_stream_capturing():
-            raise ValueError(f'inside a graph capture every input must be a device tensor; on the host: {host_inputs}')
+        _refuse_host_inputs_in_capture(host_inputs)
         if not joined:
             kp0, len0 = _join('kp0', kp0, dev)
             kp1, len1 = _join('kp1', kp1, dev)
@@ -142,7 +123,9 @@ def assemble_matches(crops, scales, kp0, kp1, matches, conf=None, offsets0=None,
             offsets1 = _upload('offsets1', offsets1, torch.int32, (P + 1,), dev)
         if P < 1:
             raise ValueError('assemble_matches needs at least one pair')
-        kp0, kp1 = _crop_keypoints('kp0', kp0, dev), _crop_keypoints('kp1', kp1, dev)
+        # rows on 8 bytes: the kernel moves a keypoint as one vector
+        kp0 = _keypoints('kp0', kp0, dev, 'geometry records', align=8, rows='K')
+        kp1 = _keypoints('kp1', kp1, dev, 'geometry records', align=8, rows='K')
         N0, N1 = int(kp0.shape[0]), int(kp1.shape[0])
         if max(N0, N1) > 2 ** 31 - 1:
             raise ValueError('more than 2^31 - 1 keypoints on a side in one call')

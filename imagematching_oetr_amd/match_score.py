@@ -16,12 +16,13 @@ tensor.
 """
 import math
 
-import numpy as np
 import torch
 
 from . import hip_engine
+from ._inputs import (_is_host, _keypoints, _offsets_of, _pair_blocks, _pair_tensor, _refuse_float64,
+                      _refuse_host_inputs_in_capture, _upload)
 from .covis_set import pair_params
-from .hip_engine import MATCH_SCORE_COUNTERS, MATCH_SCORE_PARAM_DOUBLES, _check, _stream
+from .hip_engine import MATCH_SCORE_COUNTERS, _check, _stream
 
 FLAG_DEPTH1, FLAG_DEPTH2, FLAG_EPI, FLAG_EPISYM, FLAG_REPROJ = 1, 2, 4, 8, 16
 VALUES = ('epi_ref', 'episym', 'reproj12_sq', 'reproj21_sq')
@@ -38,42 +39,6 @@ def match_params(depth_set, idx1, idx2):
     K2 = full[:, 20:29]
     return torch.cat([full[:, 16:20], K2[:, 0:1], K2[:, 4:5], K2[:, 2:3], K2[:, 5:6],
                       T[:, :3, :3].reshape(n, 9), T[:, :3, 3]], dim=1).contiguous()
-
-
-def _is_host(x):
-    return not (torch.is_tensor(x) and x.is_cuda)
-
-
-def _dtype_of(x):
-    return x.dtype if torch.is_tensor(x) else np.asarray(x).dtype
-
-
-def _refuse_float64(name, k):
-    if _dtype_of(k) in (torch.float64, np.dtype(np.float64)):
-        raise ValueError(f'{name} is float64: the score is defined on float32 keypoints (widened exactly); rounding '
-                         'float64 keypoints here would change the score. Convert them to float32 yourself.')
-
-
-def _keypoints(name, k, dev):
-    """``k`` -> contiguous float32 ``[M,2]`` on ``dev``; float16 widened; a host array is uploaded (blocking)."""
-    if _is_host(k):
-        k = torch.as_tensor(np.asarray(k) if not torch.is_tensor(k) else k)
-    if k.dtype not in (torch.float32, torch.float16):
-        raise ValueError(f'{name} must be float32 or float16, got {k.dtype}')
-    if k.dim() != 2 or k.shape[1] != 2:
-        raise ValueError(f'{name} must be [M,2], got {tuple(k.shape)}')
-    if k.is_cuda and k.device != dev:
-        raise ValueError(f'{name} is on {k.device}, the depth-map set on {dev}')
-    return k.to(device=dev, dtype=torch.float32).contiguous()       # from the host: a blocking copy
-
-
-def _upload(name, x, dtype, shape, dev):
-    """A device tensor as it is (checked), a host array by a blocking copy."""
-    if _is_host(x):
-        x = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(dtype).reshape(shape).to(dev)
-    if x.dtype != dtype or tuple(x.shape) != tuple(shape) or x.device != dev:
-        raise ValueError(f'{name} must be a {dtype} tensor of shape {tuple(shape)} on {dev}')
-    return x.contiguous()
 
 
 @torch.no_grad()
@@ -115,24 +80,20 @@ def score_matches(depth_set, pair_index, k1, k2, lengths=None, offsets=None, par
     if lengths is not None:
         host_inputs.append('lengths')
     with torch.cuda.device(dev):
-        if host_inputs and torch.cuda.is_current_stream_capturing():
-            raise ValueError(f'inside a graph capture every input must be a device tensor; on the host: {host_inputs}')
-        k1, k2 = _keypoints('k1', k1, dev), _keypoints('k2', k2, dev)
+        _refuse_host_inputs_in_capture(host_inputs)
+        k1, k2 = _keypoints('k1', k1, dev, 'depth-map set'), _keypoints('k2', k2, dev, 'depth-map set')
         M = int(k1.shape[0])
         if int(k2.shape[0]) != M:
             raise ValueError(f'k1 has {M} rows, k2 {int(k2.shape[0])}')
         if M > 2 ** 31 - 1:
             raise ValueError('more than 2^31 - 1 matches in one call')
-        if _is_host(pair_index):
-            pair_index = torch.as_tensor(np.asarray(pair_index, dtype=np.int32).reshape(-1, 2)).to(dev)
-        if pair_index.dtype != torch.int32 or pair_index.dim() != 2 or pair_index.shape[1] != 2 or pair_index.device != dev:
-            raise ValueError(f'a device pair_index must be int32 [P,2] on {dev}')
+        pair_index = _pair_tensor(dev, pair_index)
         P = int(pair_index.shape[0])
         if lengths is not None:
             lengths = [int(n) for n in lengths]
             if len(lengths) != P or any(n < 0 for n in lengths) or sum(lengths) != M:
                 raise ValueError(f'`lengths` must hold {P} non-negative lengths summing to {M} rows')
-            offsets = torch.as_tensor(np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int32)).to(dev)
+            offsets = _offsets_of(lengths, dev)
         else:
             offsets = _upload('offsets', offsets, torch.int32, (P + 1,), dev)
         if out is None:
@@ -149,12 +110,7 @@ def score_matches(depth_set, pair_index, k1, k2, lengths=None, offsets=None, par
             if values:
                 out['values'].fill_(math.nan)
             return out
-        idx1, idx2 = pair_index[:, 0].contiguous(), pair_index[:, 1].contiguous()
-        table, _ = depth_set._commit()
-        if params is None:
-            params = match_params(depth_set, idx1, idx2)
-        else:
-            params = _upload('params', params, torch.float64, (P, MATCH_SCORE_PARAM_DOUBLES), dev)
+        idx1, idx2, table, params = _pair_blocks(depth_set, pair_index, params, match_params)
         thr = [math.nan if t is None else float(t) for t in (epi_thr, sym_thr, px_thr)]
         lib = hip_engine.load_library()
         ptr = lambda t: t.data_ptr() if t.numel() else None

@@ -15,44 +15,18 @@ copy_ beyond the spread the run itself shows; that is recorded per shape (``gath
 import argparse
 import hashlib
 import json
-import statistics
 import sys
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 import torch  # noqa: E402
+from probe_common import graph_of, stats, timed  # noqa: E402
 import imagematching_oetr_amd as pkg  # noqa: E402
 
 CALLS, ROUNDS = 100, 9          # gather / copy: launches per graph, alternated rounds
 E2E_ROUNDS = 3
 IMAGES, SIZE = 64, 640
-
-
-def timed(fn):
-    """Milliseconds between two device events around ``fn()``, the device idle before and after."""
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end)
-
-
-def stats(xs):
-    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
-
-
-def graph_of(call):
-    call()                                   # warm-up: code object, workspace
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(CALLS):
-            call()
-    g.replay()
-    return g
 
 
 def gather_vs_copy(eng, dev, n, hf, wf, bank_images=64):
@@ -67,8 +41,8 @@ def gather_vs_copy(eng, dev, n, hf, wf, bank_images=64):
     dst = torch.empty_like(src)
     eng.bank_gather(bank, i1, bank, i2, t1, t2)
     assert torch.equal(t1, bank[i1.long()].reshape(-1, 256)) and torch.equal(t2, bank[i2.long()].reshape(-1, 256))
-    graphs = {'gather': graph_of(lambda: eng.bank_gather(bank, i1, bank, i2, t1, t2)),
-              'copy': graph_of(lambda: dst.copy_(src))}
+    graphs = {'gather': graph_of(lambda: eng.bank_gather(bank, i1, bank, i2, t1, t2), CALLS),
+              'copy': graph_of(lambda: dst.copy_(src), CALLS)}
     us = {k: [] for k in graphs}
     for _ in range(ROUNDS):
         for k, g in graphs.items():

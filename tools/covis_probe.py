@@ -28,6 +28,7 @@ sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REPO / 'tests'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from probe_common import graph_of, stats, timed  # noqa: E402
 import covis_oracle as cvo  # noqa: E402
 from imagematching_oetr_amd.covis import covis_boxes  # noqa: E402
 
@@ -35,32 +36,6 @@ CALLS, ROUNDS = 50, 9
 DISTINCT = 8                      # distinct scenes per size; larger batches repeat them
 KINDS = ('plane', 'plane', 'trunc', 'plane', 'no_overlap', 'plane', 'behind', 'plane')
 SHAPES = ((8, 640), (32, 640), (8, 1024))
-
-
-def timed(fn):
-    """Milliseconds between two device events around ``fn()``, the device idle before and after."""
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end)
-
-
-def stats(xs):
-    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
-
-
-def graph_of(call):
-    call()                                   # warm-up: code object
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(CALLS):
-            call()
-    g.replay()
-    return g
 
 
 def scenes_of(size):
@@ -95,8 +70,8 @@ def cell(dev, n, size, masks, arrays, expected, params):
     moved = depth_bytes + mask_bytes
     src = torch.empty(moved // 2, dtype=torch.uint8, device=dev).random_(0, 255)
     dst = torch.empty_like(src)
-    graphs = {'covis': graph_of(lambda: covis_boxes(d1, d2, prm, masks=masks, out=out)),
-              'copy': graph_of(lambda: dst.copy_(src))}
+    graphs = {'covis': graph_of(lambda: covis_boxes(d1, d2, prm, masks=masks, out=out), CALLS),
+              'copy': graph_of(lambda: dst.copy_(src), CALLS)}
     us = {k: [] for k in graphs}
     for _ in range(ROUNDS):
         for k, g in graphs.items():

@@ -36,6 +36,7 @@ sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REPO / 'tests'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from probe_common import graph_of, stats, timed  # noqa: E402
 import covis_set_oracle as cso  # noqa: E402
 from imagematching_oetr_amd import DepthSet, overlap_boxes_indexed  # noqa: E402
 from imagematching_oetr_amd.covis import covis_boxes  # noqa: E402
@@ -47,32 +48,6 @@ CELLS = (('640x640 x64, 16 pairs per image', ((640, 640),), 16),
          ('640x640 x64, 4 pairs per image', ((640, 640),), 4),
          ('480x640 / 640x480 / 640x640 x64, 16 pairs per image', ((480, 640), (640, 480), (640, 640)), 16))
 KEYS = ('overlap_box1', 'overlap_box2', 'overlap_valid', 'overlap_count')
-
-
-def timed(fn):
-    """Milliseconds between two device events around ``fn()``, the device idle before and after."""
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end)
-
-
-def stats(xs):
-    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
-
-
-def graph_of(call):
-    call()                                   # warm-up: code object
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(CALLS):
-            call()
-    g.replay()
-    return g
 
 
 def nbytes(*tensors):
@@ -108,8 +83,8 @@ def cell(dev, name, shapes, per_image):
            'pairs_restated_on_the_host': checked,
            'device_bytes': {'indexed': set_bytes + call_bytes}}
     out_g = overlap_boxes_indexed(ds, index)
-    graphs = {'indexed': graph_of(lambda: covis_boxes_indexed(table, len(ds), ds.max_pixels, idx1, idx2, params, out=out)),
-              'indexed_gather': graph_of(lambda: overlap_boxes_indexed(ds, index, out=out_g))}
+    graphs = {'indexed': graph_of(lambda: covis_boxes_indexed(table, len(ds), ds.max_pixels, idx1, idx2, params, out=out), CALLS),
+              'indexed_gather': graph_of(lambda: overlap_boxes_indexed(ds, index, out=out_g), CALLS)}
     if len(shapes) == 1:
         stacked = torch.stack(ds._maps)
         d1, d2 = stacked.index_select(0, idx1.long()), stacked.index_select(0, idx2.long())
@@ -118,9 +93,9 @@ def cell(dev, name, shapes, per_image):
         for k in KEYS:                                           # the set entry computes what the stacked entry computes
             assert torch.equal(out[k], out_a[k]), k
         out_b = {k: v.clone() for k, v in out_a.items()}
-        graphs['stacked'] = graph_of(lambda: covis_boxes(d1, d2, params, out=out_a))
+        graphs['stacked'] = graph_of(lambda: covis_boxes(d1, d2, params, out=out_a), CALLS)
         graphs['select'] = graph_of(lambda: covis_boxes(stacked.index_select(0, idx1.long()),
-                                                        stacked.index_select(0, idx2.long()), params, out=out_b))
+                                                        stacked.index_select(0, idx2.long()), params, out=out_b), CALLS)
         pair_maps = nbytes(d1, d2)
         rec['device_bytes']['stacked'] = pair_maps + call_bytes - nbytes(idx1, idx2)
         rec['device_bytes']['select'] = nbytes(stacked) + pair_maps + call_bytes

@@ -20,14 +20,13 @@ import argparse
 import ctypes as C
 import hashlib
 import json
-import statistics
 import sys
-import time
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 import torch  # noqa: E402
+from probe_common import graph_of, stats, timed, wall  # noqa: E402
 import imagematching_oetr_amd as pkg  # noqa: E402
 from imagematching_oetr_amd.hip_engine import _CropInfo, _check, _stream  # noqa: E402
 
@@ -35,41 +34,6 @@ CALLS, REPLAYS, ROUNDS, ITERS = 10, 40, 9, 20      # a device window is 400 call
 H, W, FRAME = 480, 640, 640
 SCALES = (W / FRAME, H / FRAME)          # overlap_scales of a 640 x 480 matcher image under a 640 x 640 OETR frame
 CELLS = [(n, c, d) for n in (8, 32) for c in (1, 3) for d in (1, 8)]
-
-
-def timed(fn):
-    """Milliseconds between two device events around ``fn()``, the device idle before and after."""
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end)
-
-
-def wall(fn):
-    """Milliseconds of host wall time of ``fn()`` up to the end of its device work."""
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) * 1e3
-
-
-def stats(xs):
-    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
-
-
-def graph_of(call):
-    call()                                   # warm-up: code object
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(CALLS):
-            call()
-    g.replay()
-    return g
 
 
 def boxes(n, gen):
@@ -108,8 +72,8 @@ def cell(dev, n, channels, divisor):
                 ims0[k].data_ptr(), ims1[k].data_ptr(), channels, H, W, H, W, b0[k].data_ptr(), b1[k].data_ptr(), sc, sc,
                 1, divisor, 0, tmp[k].data_ptr(), out[k, 0].data_ptr(), out[k, 1].data_ptr(), cap, info[k].data_ptr(),
                 _stream(dev)), 'oetr_overlap_crop')
-    graphs = {'batched': graph_of(lambda: pkg.overlap_crop_batch(table, b0, b1, True, divisor, out=held)),
-              'per_pair': graph_of(per_pair_entry)}
+    graphs = {'batched': graph_of(lambda: pkg.overlap_crop_batch(table, b0, b1, True, divisor, out=held), CALLS),
+              'per_pair': graph_of(per_pair_entry, CALLS)}
     for k in range(n):                       # the yardstick ran on the same pairs
         assert torch.equal(out[k, 0, :held.crop(k, 0).numel()], held.crop(k, 0).reshape(-1)), k
     eager = {'batched': lambda: [pkg.overlap_crop_batch(table, b0, b1, True, divisor, out=held) for _ in range(ITERS)],

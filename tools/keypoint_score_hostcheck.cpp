@@ -9,21 +9,15 @@
 //      these calls are SKIPPED - they would enqueue kernels on host addresses - and the program says so.
 //
 // Build and run (tools/README.md):  make -C imagematching_oetr_amd/csrc hostcheck-keypoints
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 
-#include "../include/oetr_hip.h"
 #include "../include/oetr_keypoint_score.h"
+#include "hostcheck.h"
 
 namespace {
 
-int failures = 0;
-unsigned char keep[64];
+const char ENTRY[] = "oetr_keypoint_repeatability";
 const double thresholds[8] = {1.0, 2.0, 3.0, 5.0, 8.0, 13.0, 21.0, 34.0};
 
 struct Args {
@@ -62,32 +56,16 @@ oetr_status call(const Args& a) {
                                      a.n_pairs, a.thr, a.n_thr, a.max_kp, a.counts, a.nearest, a.dist_sq, nullptr);
 }
 
-void expect(const char* what, const Args& a, oetr_status want) {
-  const oetr_status got = call(a);
-  const char* msg = oetr_last_error();
-  bool ok = got == want && msg && std::strncmp(msg, "oetr_keypoint_repeatability", 27) == 0;
-  for (unsigned char c : keep) ok = ok && c == 0xA5;
-  std::printf("%-30s status %d (want %d) %s\n", what, (int)got, (int)want, ok ? "ok" : "FAILED");
-  if (!ok) {
-    std::printf("    last error: %s\n", msg ? msg : "(null)");
-    ++failures;
-  }
-}
-
 }  // namespace
 
 int main() {
-  std::memset(keep, 0xA5, sizeof keep);
+  hostcheck::begin();
   if (oetr_keypoint_score_abi_version() != OETR_KEYPOINT_SCORE_ABI_VERSION) {
     std::printf("ABI version %d != %d\n", oetr_keypoint_score_abi_version(), OETR_KEYPOINT_SCORE_ABI_VERSION);
     return 1;
   }
-  const Args good = pointing_at(keep);
+  const Args good = pointing_at(hostcheck::keep);
   Args a;
-#define REJECT(name, edit, status) \
-  a = good;                        \
-  edit;                            \
-  expect(name, a, status)
   REJECT("maps = NULL", a.maps = nullptr, OETR_ERR_BAD_ARG);
   REJECT("kp_offsets = NULL", a.kp_offsets = nullptr, OETR_ERR_BAD_ARG);
   REJECT("idx1 = NULL", a.idx1 = nullptr, OETR_ERR_BAD_ARG);
@@ -112,21 +90,8 @@ int main() {
   REJECT("n_pairs = INT32_MAX", a.n_pairs = INT32_MAX, OETR_ERR_BAD_SHAPE);
   REJECT("n_pairs = 2^28, 8 thresholds", (a.n_pairs = 1 << 28, a.n_thr = 8, a.max_kp = 1), OETR_ERR_BAD_SHAPE);
   REJECT("max_kp = INT32_MAX, 2^20 pairs", (a.max_kp = INT32_MAX, a.n_pairs = 1 << 20), OETR_ERR_BAD_SHAPE);
-#undef REJECT
 
-  int devices = 0;
-  const hipError_t e = hipGetDeviceCount(&devices);
-  if (e == hipSuccess && devices > 0) {
-    std::printf("a GPU is visible: the PROT_NONE calls are SKIPPED (they would enqueue on host addresses); run this "
-                "program on a machine without one\n");
-  } else {
-    (void)hipGetLastError();
-    const size_t page = 1 << 16;
-    void* none = mmap(nullptr, page, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (none == MAP_FAILED) {
-      std::perror("mmap");
-      return 1;
-    }
+  if (char* none = hostcheck::no_device_page()) {
     struct Case {
       const char* name;
       int64_t n_keypoints;
@@ -139,7 +104,7 @@ int main() {
                           {"largest", INT32_MAX, 40000, 8, 6000, true},
                           {"widest", INT32_MAX, 1, 1, INT32_MAX, true}};
     for (const Case& c : cases) {
-      a = pointing_at(static_cast<char*>(none) + 256);
+      a = pointing_at(none + 256);
       a.n_keypoints = c.n_keypoints;
       a.n_pairs = c.n_pairs;
       a.n_thr = c.n_thr;
@@ -150,14 +115,8 @@ int main() {
         a.nearest = nullptr;
         a.dist_sq = nullptr;
       }
-      const oetr_status got = call(a);
-      const bool ok = got == OETR_ERR_HIP;
-      std::printf("PROT_NONE, %-28s status %d (want %d: no device) %s\n    last error: %s\n", c.name, (int)got,
-                  (int)OETR_ERR_HIP, ok ? "ok" : "FAILED", oetr_last_error());
-      failures += !ok;
+      hostcheck::expect_no_device(c.name, a);
     }
-    munmap(none, page);
   }
-  std::printf(failures ? "%d check(s) FAILED\n" : "all checks passed\n", failures);
-  return failures ? 1 : 0;
+  return hostcheck::finish();
 }

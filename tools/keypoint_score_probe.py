@@ -43,6 +43,7 @@ sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REPO / 'tests'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from probe_common import graph_of, stats, timed  # noqa: E402
 import keypoint_score_oracle as kso  # noqa: E402
 import match_score_oracle as mso  # noqa: E402
 
@@ -53,32 +54,6 @@ HOST_PAIRS = 4                      # pairs the numpy restatement is timed on (a
 TORCH_PAIRS = 16                    # pairs the torch yardstick is timed on
 ESTIMATE = {'f64_valu_issues_per_distance': 9, 'ms_for_1024_pairs': 2.0}
 MAX_CLOCK_HZ = 2.4e9                # the part's maximum engine clock: the issue count it implies is an UPPER bound
-
-
-def timed(fn):
-    """Milliseconds between two device events around ``fn()``, the device idle before and after."""
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end)
-
-
-def stats(xs):
-    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
-
-
-def graph_of(call):
-    call()                                   # warm-up: code object
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(CALLS):
-            call()
-    g.replay()
-    return g
 
 
 def host_yardstick(views, kps, pairs, blocks):
@@ -152,8 +127,8 @@ def cell(dev, ds, views, kps, name, per_image, dry_run):
         for s, w in enumerate(want[p]):
             ours = out['dist_sq'][p, s].cpu().numpy()[w['kept']]
             assert mso.rel_diff(keep[2 * p + s].cpu().numpy(), ours) < 1e-9, (p, s)
-    graphs = {'scored': graph_of(lambda: call(out=out)), 'counters_only': graph_of(lambda: call(nearest=False, out=bare)),
-              'torch': graph_of(torch_loop)}
+    graphs = {'scored': graph_of(lambda: call(out=out), CALLS), 'counters_only': graph_of(lambda: call(nearest=False, out=bare), CALLS),
+              'torch': graph_of(torch_loop, CALLS)}
     us = {k: [] for k in graphs}
     for _ in range(ROUNDS):
         for k, g in graphs.items():

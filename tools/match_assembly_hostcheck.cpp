@@ -9,20 +9,14 @@
 //      addresses - and the program says so.
 //
 // Build and run (tools/README.md):  make -C imagematching_oetr_amd/csrc hostcheck-assembly
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 
-#include "../include/oetr_hip.h"
 #include "../include/oetr_match_assembly.h"
+#include "hostcheck.h"
 
 namespace {
 
-int failures = 0;
-alignas(16) unsigned char keep[64];
+const char ENTRY[] = "oetr_assemble_matches";
 
 struct Args {
   const oetr_crop_info* info;
@@ -73,22 +67,10 @@ oetr_status call(const Args& a) {
                                nullptr);
 }
 
-void expect(const char* what, const Args& a, oetr_status want) {
-  const oetr_status got = call(a);
-  const char* msg = oetr_last_error();
-  bool ok = got == want && msg && std::strncmp(msg, "oetr_assemble_matches", 21) == 0;
-  for (unsigned char c : keep) ok = ok && c == 0xA5;
-  std::printf("%-32s status %d (want %d) %s\n", what, (int)got, (int)want, ok ? "ok" : "FAILED");
-  if (!ok) {
-    std::printf("    last error: %s\n", msg ? msg : "(null)");
-    ++failures;
-  }
-}
-
 }  // namespace
 
 int main() {
-  std::memset(keep, 0xA5, sizeof keep);
+  hostcheck::begin();
   if (oetr_match_assembly_abi_version() != OETR_MATCH_ASSEMBLY_ABI_VERSION) {
     std::printf("ABI version %d != %d\n", oetr_match_assembly_abi_version(), OETR_MATCH_ASSEMBLY_ABI_VERSION);
     return 1;
@@ -97,14 +79,10 @@ int main() {
       oetr_match_assembly_workspace_bytes(1000) < 4000 ||
       oetr_match_assembly_workspace_bytes(INT32_MAX) < (size_t)INT32_MAX * 4) {
     std::printf("oetr_match_assembly_workspace_bytes FAILED\n");
-    ++failures;
+    ++hostcheck::failures;
   }
-  const Args good = pointing_at(keep);
+  const Args good = pointing_at(hostcheck::keep);
   Args a;
-#define REJECT(name, edit, status) \
-  a = good;                        \
-  edit;                            \
-  expect(name, a, status)
   REJECT("info = NULL", a.info = nullptr, OETR_ERR_BAD_ARG);
   REJECT("scales = NULL", a.scales = nullptr, OETR_ERR_BAD_ARG);
   REJECT("kp0 = NULL", a.kp0 = nullptr, OETR_ERR_BAD_ARG);
@@ -135,43 +113,26 @@ int main() {
   REJECT("match_bytes = 16", a.match_bytes = 16, OETR_ERR_BAD_ARG);
   REJECT("match_bytes = -8", a.match_bytes = -8, OETR_ERR_BAD_ARG);
   REJECT("min_matches = -1", a.min_matches = -1, OETR_ERR_BAD_ARG);
-  REJECT("kp0 at 4 bytes", a.kp0 = reinterpret_cast<const float*>(keep + 4), OETR_ERR_BAD_ARG);
-  REJECT("origin0 at 8 bytes", a.origin0 = reinterpret_cast<double*>(keep + 8), OETR_ERR_BAD_ARG);
-  REJECT("int64 matches at 4 bytes", (a.matches = keep + 4, a.match_bytes = 8), OETR_ERR_BAD_ARG);
+  REJECT("kp0 at 4 bytes", a.kp0 = reinterpret_cast<const float*>(hostcheck::keep + 4), OETR_ERR_BAD_ARG);
+  REJECT("origin0 at 8 bytes", a.origin0 = reinterpret_cast<double*>(hostcheck::keep + 8), OETR_ERR_BAD_ARG);
+  REJECT("int64 matches at 4 bytes", (a.matches = hostcheck::keep + 4, a.match_bytes = 8), OETR_ERR_BAD_ARG);
   REJECT("n_kp0 = 2^31", a.n_kp0 = (int64_t)1 << 31, OETR_ERR_BAD_SHAPE);
   REJECT("n_kp1 = INT64_MAX", a.n_kp1 = INT64_MAX, OETR_ERR_BAD_SHAPE);
   REJECT("n_pairs = INT32_MAX", a.n_pairs = INT32_MAX, OETR_ERR_BAD_SHAPE);
   REJECT("workspace_bytes = 0", a.workspace_bytes = 0, OETR_ERR_WORKSPACE);
   REJECT("workspace one byte short", (a.n_pairs = 100000, a.workspace_bytes = oetr_match_assembly_workspace_bytes(100000) - 1),
          OETR_ERR_WORKSPACE);
-#undef REJECT
 
-  int devices = 0;
-  const hipError_t e = hipGetDeviceCount(&devices);
-  if (e == hipSuccess && devices > 0) {
-    std::printf("a GPU is visible: the PROT_NONE calls are SKIPPED (they would enqueue on host addresses); run this "
-                "program on a machine without one\n");
-  } else {
-    (void)hipGetLastError();
-    const size_t page = 1 << 16;
-    void* none = mmap(nullptr, page, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (none == MAP_FAILED) {
-      std::perror("mmap");
-      return 1;
-    }
+  if (char* none = hostcheck::no_device_page()) {
     for (int variant = 0; variant < 4; ++variant) {
-      a = pointing_at(static_cast<char*>(none) + 256);
+      a = pointing_at(none + 256);
       if (variant == 1) a.n_kp0 = a.n_kp1 = 0, a.kp0 = a.kp1 = nullptr, a.matches = nullptr, a.origin0 = nullptr;
       if (variant == 2) a.n_kp0 = a.n_kp1 = INT32_MAX, a.n_pairs = 40000, a.match_bytes = 8;
       if (variant == 3) a.conf = nullptr, a.mconf = nullptr, a.few = a.n_few = nullptr;
-      const oetr_status got = call(a);
-      const bool ok = got == OETR_ERR_HIP;
-      std::printf("PROT_NONE, variant %d          status %d (want %d: no device) %s\n    last error: %s\n", variant,
-                  (int)got, (int)OETR_ERR_HIP, ok ? "ok" : "FAILED", oetr_last_error());
-      failures += !ok;
+      char label[16];
+      std::snprintf(label, sizeof label, "variant %d", variant);
+      hostcheck::expect_no_device(label, a);
     }
-    munmap(none, page);
   }
-  std::printf(failures ? "%d check(s) FAILED\n" : "all checks passed\n", failures);
-  return failures ? 1 : 0;
+  return hostcheck::finish();
 }

@@ -40,6 +40,7 @@ sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REPO / 'tests'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from probe_common import graph_of, stats, timed  # noqa: E402
 import match_assembly_oracle as mao  # noqa: E402
 
 CALLS, ROUNDS = 10, 9
@@ -48,32 +49,6 @@ BYTES_PER_ROW0 = {'kp0': 8, 'matches': 4, 'conf': 4, 'origin0': 16, 'index0': 4,
 BYTES_PER_ROW1 = {'kp1': 8, 'origin1': 16}
 HOST_PAIRS = 32                     # pairs route (b) is timed on
 CHECKED_PAIRS = 8                   # pairs checked against the specification
-
-
-def timed(fn):
-    """Milliseconds between two device events around ``fn()``, the device idle before and after."""
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end)
-
-
-def stats(xs):
-    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
-
-
-def graph_of(call):
-    call()                                   # warm-up: code object
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(CALLS):
-            call()
-    g.replay()
-    return g
 
 
 def make_inputs(P, K, seed):
@@ -188,7 +163,7 @@ def cell(dev, name, P, K, dry_run):
     total_bytes = rec['algorithmic_bytes_total']
     src, dst = (torch.empty(total_bytes // 2, dtype=torch.uint8, device=dev) for _ in range(2))
     src.zero_()
-    graphs = {'assembled': graph_of(lambda: assemble_matches(**t, out=out)), 'copy': graph_of(lambda: dst.copy_(src))}
+    graphs = {'assembled': graph_of(lambda: assemble_matches(**t, out=out), CALLS), 'copy': graph_of(lambda: dst.copy_(src), CALLS)}
     eager = {'assembled_eager': lambda: [assemble_matches(**t, out=out) for _ in range(CALLS)],
              'torch': lambda: [torch_route(t, P, K) for _ in range(CALLS)]}
     for fn in eager.values():

@@ -9,21 +9,15 @@
 //      addresses - and the program says so.
 //
 // Build and run (tools/README.md):  make -C imagematching_oetr_amd/csrc hostcheck
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 
-#include "../include/oetr_hip.h"
 #include "../include/oetr_match_score.h"
+#include "hostcheck.h"
 
 namespace {
 
-int failures = 0;
-unsigned char keep[64];
+const char ENTRY[] = "oetr_match_score";
 
 struct Args {
   const oetr_covis_map* maps;
@@ -63,32 +57,16 @@ oetr_status call(const Args& a) {
                           a.epi, a.sym, a.px, a.values, a.flags, a.counts, nullptr);
 }
 
-void expect(const char* what, const Args& a, oetr_status want) {
-  const oetr_status got = call(a);
-  const char* msg = oetr_last_error();
-  bool ok = got == want && msg && std::strncmp(msg, "oetr_match_score", 16) == 0;
-  for (unsigned char c : keep) ok = ok && c == 0xA5;
-  std::printf("%-28s status %d (want %d) %s\n", what, (int)got, (int)want, ok ? "ok" : "FAILED");
-  if (!ok) {
-    std::printf("    last error: %s\n", msg ? msg : "(null)");
-    ++failures;
-  }
-}
-
 }  // namespace
 
 int main() {
-  std::memset(keep, 0xA5, sizeof keep);
+  hostcheck::begin();
   if (oetr_match_score_abi_version() != OETR_MATCH_SCORE_ABI_VERSION) {
     std::printf("ABI version %d != %d\n", oetr_match_score_abi_version(), OETR_MATCH_SCORE_ABI_VERSION);
     return 1;
   }
-  const Args good = pointing_at(keep);
+  const Args good = pointing_at(hostcheck::keep);
   Args a;
-#define REJECT(name, edit, status) \
-  a = good;                        \
-  edit;                            \
-  expect(name, a, status)
   REJECT("maps = NULL", a.maps = nullptr, OETR_ERR_BAD_ARG);
   REJECT("idx1 = NULL", a.idx1 = nullptr, OETR_ERR_BAD_ARG);
   REJECT("idx2 = NULL", a.idx2 = nullptr, OETR_ERR_BAD_ARG);
@@ -108,33 +86,16 @@ int main() {
   REJECT("n_matches = 2^31", a.n_matches = (int64_t)1 << 31, OETR_ERR_BAD_SHAPE);
   REJECT("n_matches = INT64_MAX", a.n_matches = INT64_MAX, OETR_ERR_BAD_SHAPE);
   REJECT("n_pairs = INT32_MAX", a.n_pairs = INT32_MAX, OETR_ERR_BAD_SHAPE);
-#undef REJECT
 
-  int devices = 0;
-  const hipError_t e = hipGetDeviceCount(&devices);
-  if (e == hipSuccess && devices > 0) {
-    std::printf("a GPU is visible: the PROT_NONE call is SKIPPED (it would enqueue on host addresses); run this "
-                "program on a machine without one\n");
-  } else {
-    (void)hipGetLastError();
-    const size_t page = 1 << 16;
-    void* none = mmap(nullptr, page, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (none == MAP_FAILED) {
-      std::perror("mmap");
-      return 1;
-    }
+  if (char* none = hostcheck::no_device_page()) {
     for (int64_t n : {(int64_t)5, (int64_t)0, (int64_t)INT32_MAX}) {
-      a = pointing_at(static_cast<char*>(none) + 256);
+      a = pointing_at(none + 256);
       a.n_matches = n;
       a.n_pairs = n == 5 ? 2 : 40000;
-      const oetr_status got = call(a);
-      const bool ok = got == OETR_ERR_HIP;
-      std::printf("PROT_NONE, n_matches %-10lld status %d (want %d: no device) %s\n    last error: %s\n", (long long)n,
-                  (int)got, (int)OETR_ERR_HIP, ok ? "ok" : "FAILED", oetr_last_error());
-      failures += !ok;
+      char label[32];
+      std::snprintf(label, sizeof label, "n_matches %lld", (long long)n);
+      hostcheck::expect_no_device(label, a);
     }
-    munmap(none, page);
   }
-  std::printf(failures ? "%d check(s) FAILED\n" : "all checks passed\n", failures);
-  return failures ? 1 : 0;
+  return hostcheck::finish();
 }

@@ -35,6 +35,7 @@ sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REPO / 'tests'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from probe_common import graph_of, stats, timed  # noqa: E402
 import match_score_oracle as mso  # noqa: E402
 
 CALLS, ROUNDS = 10, 9
@@ -42,32 +43,6 @@ CELLS = (('16 pairs per image', 16), ('4 pairs per image', 4))
 THR = dict(epi_thr=5e-4, sym_thr=1e-4, px_thr=3.0)
 BYTES_PER_MATCH = {'keypoints': 16, 'values': 32, 'flags': 1, 'depth': 8}
 HOST_PAIRS = 4                      # pairs the numpy restatement is timed on (and the device results checked against)
-
-
-def timed(fn):
-    """Milliseconds between two device events around ``fn()``, the device idle before and after."""
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end)
-
-
-def stats(xs):
-    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
-
-
-def graph_of(call):
-    call()                                   # warm-up: code object
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(CALLS):
-            call()
-    g.replay()
-    return g
 
 
 def make_inputs(views, per_image, n_matches):
@@ -125,8 +100,8 @@ def cell(dev, ds, views, name, per_image, n_matches, dry_run):
     total = rec['algorithmic_bytes_total']
     src, dst = (torch.empty(total // 2, dtype=torch.uint8, device=dev) for _ in range(2))
     src.zero_()
-    graphs = {'scored': graph_of(lambda: call(out=out)), 'flags_only': graph_of(lambda: call(values=False, out=bare)),
-              'copy': graph_of(lambda: dst.copy_(src))}
+    graphs = {'scored': graph_of(lambda: call(out=out), CALLS), 'flags_only': graph_of(lambda: call(values=False, out=bare), CALLS),
+              'copy': graph_of(lambda: dst.copy_(src), CALLS)}
     us = {k: [] for k in graphs}
     for _ in range(ROUNDS):
         for k, g in graphs.items():
