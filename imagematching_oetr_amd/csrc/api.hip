@@ -1,14 +1,16 @@
-// C ABI of liboetr_hip.so (declared in include/oetr_hip.h): weight repacking,
-// workspace layout and launch orchestration.  No torch types, no hidden
+// C ABI of liboetr_hip.so (declared in include/oetr_hip.h; the tail-sharing switch in
+// include/oetr_tail_share.h): weight repacking, workspace layout and launch orchestration.  No torch types, no hidden
 // allocation or synchronisation inside forward calls.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <string>
 #include <vector>
 
 #include "../../include/oetr_hip.h"
+#include "../../include/oetr_tail_share.h"
 #include "common.h"
 
 using namespace oetr;
@@ -150,6 +152,9 @@ struct oetr_ctx {
   int device = 0;
   int mode = GM_SPLIT;  // GEMM mode GM_* (common.h) of the oetr_dtype
   int kv_prereduce = -1; // oetr_set_state_prereduce (-1 = auto)
+  int tail_share = -1;   // oetr_set_tail_share (-1 = auto, 0 = off)
+  mutable std::atomic<int> enc_grid{0};   // oetr_debug_encoder_grid: workgroups of the most recent encoder launch (forward
+                                          // calls on several threads share a handle: a relaxed store, read by tests only)
   mutable int dec_fault = 0;   // oetr_debug_decoder_fault: one shot, consumed by the next four-workgroup decoder launch
   int dec_split = 0;     // oetr_set_decoder_split: 0 auto, 1 one workgroup per image, 4 four (decoder.hip: decoder_body4)
   int tail_mode = 0;     // oetr_set_tail_mode: 0 auto, 1 P form (decoder || conv-P, combine), 2 direct (decoder, conv)
@@ -404,6 +409,11 @@ oetr_status run_correlation(oetr_ctx* h, const Geom& g, const Workspace& w, cons
   }
   p.tile_rows = encoder_tile_rows(h, g);
   p.g = encoder_geom(g, p.tile_rows);
+  // oetr_set_tail_share: a pair's two ragged last tiles in one workgroup where the launch can (encoder.hip:
+  // encoder_tail_share) - at 400 tokens per image 13 workgroups per pair instead of 14, bit-identical results
+  p.tail_share = h->tail_share != 0;
+  p.attn_full = h->attn_full;
+  h->enc_grid.store(encoder_workgroups(p, h->mode), std::memory_order_relaxed);
 #ifdef OETR_ABLATE
   { const char* e = getenv("OETR_ABLATE"); p.dbg = e ? atoi(e) : 0; }
 #endif
@@ -418,7 +428,6 @@ oetr_status run_correlation(oetr_ctx* h, const Geom& g, const Workspace& w, cons
   p.x = w.x; p.qp = w.qp; p.pos = w.pos;
   p.mask[0] = mask1; p.mask[1] = mask2;
   p.flags = w.flags;
-  p.attn_full = h->attn_full;
   p.policy = h->policy;
   for (int i = 0; i < 2; ++i) p.lpad[i] = g.nt[i] * TM;
   p.vt_off[0] = 0; p.vt_off[1] = (size_t)g.N * C * p.lpad[0];
@@ -1475,6 +1484,15 @@ oetr_status oetr_set_state_prereduce(oetr_handle h, int on) {
   h->kv_prereduce = on;
   return OETR_OK;
 }
+
+oetr_status oetr_set_tail_share(oetr_handle h, int mode) {
+  if (!h) return fail(OETR_ERR_BAD_ARG, "oetr_set_tail_share: NULL handle");
+  if (mode != -1 && mode != 0) return fail(OETR_ERR_BAD_ARG, "oetr_set_tail_share: -1 (auto) or 0 (off)");
+  h->tail_share = mode;
+  return OETR_OK;
+}
+
+int oetr_debug_encoder_grid(oetr_handle h) { return h ? h->enc_grid.load(std::memory_order_relaxed) : -1; }
 
 oetr_status oetr_set_attention(oetr_handle h, oetr_attention mode) {
   if (!h) return fail(OETR_ERR_BAD_ARG, "oetr_set_attention: NULL handle");

@@ -1152,6 +1152,10 @@ struct EncLaunch {
   size_t vt_off[2];      // first float of the side's images in vt
   int tile_rows;         // token rows per workgroup: 32 (TM) or 64 (split mode, k_encoder64);
                          // g.nt / g.tile0 / g.ntiles are in units of this tile
+  int nwg;               // workgroups of the launch: g.ntiles, or one fewer per pair with tail_share
+  int tail_share;        // k_encoder64, two-plane modes: a pair's two ragged last tiles (1..16 rows each) run in
+                         // ONE workgroup, as rows 0.. and 16.. of one 32-row MFMA tile (encoder64_body: Seg2);
+                         // g.ntiles / g.nt keep counting SLOTS (the heads and the decoder share Geom)
   int b_cross;           // phase-B layer is a cross layer
   int kv_reduced;        // kv_in / ks_in hold ONE reduced state per image ([2N][8192] / [2N][256], side 0
                          // first) instead of per-tile partials: k_kv_reduce ran between the launches
@@ -1175,7 +1179,10 @@ struct EncLaunch {
 
 // has_b: run phase B (finish a layer); tail: 0 = phase A of next encoder layer,
 // 1 = decoder K/V preparation, 2 = nothing.
+// (p.tail_share on entry: 0 = off, else wanted - the launch decides, see encoder_tail_share; p.nwg is the launch's own)
 hipError_t launch_encoder(const EncLaunch& p, bool has_b, int tail, int mode, hipStream_t s);
+// Workgroups launch_encoder launches for p: g.ntiles, or one per pair fewer where it shares the ragged last tiles.
+int encoder_workgroups(const EncLaunch& p, int mode);
 // Sum the per-tile partial linear-attention states of every image (fixed tile order) once,
 // between the launch that wrote them and the launch whose every workgroup would otherwise
 // re-reduce them: g = the ENCODER tile geometry; kvr [2N][8192], ksr [2N][256].

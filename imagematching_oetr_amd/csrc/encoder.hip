@@ -170,17 +170,21 @@ __device__ __forceinline__ void load_tile(float* S, const float* __restrict__ sr
 // The same tile from the reference's layout: src -> element (channel 0, token l0) of an
 // image's [256][L] map; S[r][c] = src[c * L + r].  A half-wave reads 32 consecutive tokens
 // of one channel (128 B); the transposed LDS writes are 2-way conflicted (row stride 260).
+// (s: channel 0 of the token that row tid % ROWS of the tile holds - the caller's row clamp applied)
 template <int THREADS, int ROWS>
-__device__ __forceinline__ void load_tile_nchw(float* S, const float* __restrict__ src, int L,
-                                               int nvalid, int tid) {
+__device__ __forceinline__ void load_rows_nchw(float* S, const float* __restrict__ s, int L, int tid) {
   constexpr int CG = THREADS / ROWS;
   const int r = tid % ROWS, cg = tid / ROWS;
-  const float* s = src + min(r, nvalid - 1);
 #pragma unroll
   for (int i = 0; i < C / CG; ++i) {
     const int c = cg + CG * i;
     S[r * LDA + c] = s[(size_t)c * L];
   }
+}
+template <int THREADS, int ROWS>
+__device__ __forceinline__ void load_tile_nchw(float* S, const float* __restrict__ src, int L,
+                                               int nvalid, int tid) {
+  load_rows_nchw<THREADS, ROWS>(S, src + min(tid % ROWS, nvalid - 1), L, tid);
 }
 // ... and back out token-major (rows of 1 KB): dst -> row l0 of a [L][256] table
 template <int THREADS, int ROWS>
@@ -897,7 +901,10 @@ struct E2 {
 // MASKED (forward_dummy's masks, linear_attention.py:37-41): msk_s[row] = the token's kv_mask value,
 // 0 past the tile's last valid row - it multiplies phi(K) and V where the unmasked form has the
 // row-validity 1 / 0 (an instantiation of its own: the default path's instruction stream is untouched).
-template <int MODE, int NMT = 2, bool MASKED = false>
+// LO16 (second segment of a shared ragged tile, encoder64_body: Seg2): the segment's rows are 16 .. nvalid - 1 -
+// rows 0..15 (k16 step 0 of the split form, registers 0..7) belong to the other image and get the mask 0 like every
+// row past the end (MASKED: msk_s holds the zeros).
+template <int MODE, int NMT = 2, bool MASKED = false, bool LO16 = false>
 __device__ __forceinline__ void kv_state_64(const f32x16 (&accK)[NMT], const f32x16 (&accV)[NMT],
                                             int S_len, int nvalid, int half, bool two, f32x16& kv,
                                             float& ksum, Range& rg, const float* msk_s = nullptr) {
@@ -934,6 +941,7 @@ __device__ __forceinline__ void kv_state_64(const f32x16 (&accK)[NMT], const f32
           const int r = 8 * st + i;
           float m;
           if constexpr (MASKED) m = msk_s[32 * mt + crow(r, half)];
+          else if constexpr (LO16) m = (r >= 8 && 32 * mt + crow(r, 0) < nv2) ? 1.0f : 0.0f;
           else m = 32 * mt + crow(r, 0) < nv2 ? 1.0f : 0.0f;
           const float kk = elu1(accK[mt][r]) * m;
           const float vv = accV[mt][r] * (inv_len * m);
@@ -963,6 +971,7 @@ __device__ __forceinline__ void kv_state_64(const f32x16 (&accK)[NMT], const f32
       auto operands = [&](int r, float& k, float& v) {
         float m;
         if constexpr (MASKED) m = msk_s[32 * mt + crow(r, half)];
+        else if constexpr (LO16) m = (r >= 8 && 32 * mt + crow(r, 0) < nv2) ? 1.0f : 0.0f;
         else m = 32 * mt + crow(r, 0) < nv2 ? 1.0f : 0.0f;
         const float x = accK[mt][r];
         k = (elu1(x)) * m;
@@ -999,6 +1008,25 @@ __device__ __forceinline__ void kv_state_write(const f32x16& kv, float ksum, int
   if (lane < 32) (ks_out + (size_t)slot * C + wave * HD)[(unsigned)lane] = ksum;
 }
 
+// Which tile a workgroup of k_encoder64 / k_encoder32m runs (pair-major logical order, an XCD owns whole pairs).
+// Without tail sharing a pair is image 1's tiles, then image 2's.  With it (EncLaunch::tail_share) a pair is image
+// 1's full tiles, image 2's full tiles, then ONE workgroup for both ragged last tiles: `shared`, identified as
+// image 1's last tile (side 0, t_idx nt[0] - 1).
+struct EncWg { int n, side, t_idx; bool shared; };
+__device__ __forceinline__ EncWg enc_wg(const EncLaunch& p) {
+  const Geom& g = p.g;
+  const int logical = xcd_remap(blockIdx.x, p.nwg);
+  const int f0 = g.nt[0] - p.tail_share;              // image 1's tiles that come first in a pair
+  const int per = f0 + g.nt[1];
+  EncWg w;
+  w.n = logical / per;
+  const int rem = logical - w.n * per;
+  w.shared = p.tail_share != 0 && rem == per - 1;
+  w.side = !w.shared && rem >= f0;
+  w.t_idx = w.shared ? f0 : w.side ? rem - f0 : rem;
+  return w;
+}
+
 // Body of k_encoder64 for one workgroup.  ROWS (WStream2T): 2 = both 32-row MFMA tiles hold valid
 // rows, 1 = only the first does (a ragged last tile of an image: every piece of work on the
 // second row tile is compiled out), 0 = decided at run time (single-plane modes).
@@ -1024,6 +1052,9 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
   float* ksum_s = smem + L2::KSUM;
   float* lnp_s = smem + L2::LNP;
   float* lnx_s = smem + L2::LNX;
+  // (Seg2: Ksum of segment 2's source image, in the exchange rows 32.. that a one-row-tile workgroup never reads;
+  //  written before the first barrier, last read before the one that ends the apply - the exchange comes later)
+  float* ksum2_s = lnx_s + 32 * LNX_LD;
   using WS = WStream2T<MODE, ROWS, NMT>;
   WS ws;
   constexpr int P_MERGE = 0;
@@ -1041,12 +1072,8 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
   const int wcol = 32 * wave;
   const int lrow = tid / TPR, lpart = tid % TPR;
 
-  const int logical = xcd_remap(blockIdx.x, g.ntiles);
-  const int per = g.nt[0] + g.nt[1];
-  const int n = logical / per;
-  const int rem = logical - n * per;
-  const int side = rem >= g.nt[0];
-  const int t_idx = side ? rem - g.nt[0] : rem;
+  const EncWg wg = enc_wg(p);
+  const int n = wg.n, side = wg.side, t_idx = wg.t_idx;
   const int L = g.L[side];
   const int l0 = t_idx * RTW;
   const int nvalid = min(RTW, L - l0);
@@ -1057,10 +1084,29 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
   ws.set_rows(nvalid);
   ws.set_lane(lane);
 
+  // Seg2: the one-row-tile body runs TWO segments of its 32-row MFMA tile - segment 1 = rows [0, nvalid) of this
+  // tile, segment 2 = rows [16, 16 + r2) with image 2's ragged last tile of the same pair (EncLaunch::tail_share:
+  // both tails are then at most 16 rows).  An unshared ragged tile is the same code with r2 = 0: the arithmetic
+  // blocks (apply, states) are ONE instruction stream with the masks applied unconditionally (file header: no
+  // run-time choice between two forms of the state), only segment 2's loads and stores sit behind the
+  // wave-uniform r2 != 0.  With r2 = 0 segment 2's bases repeat segment 1's: every address formed from them is valid.
+  constexpr bool Seg2 = ROWS == 1 && RTW == RT;
+  static_assert(!Seg2 || gm_f16_range(MODE), "one-row-tile body: two-plane modes");
+  const int r2 = Seg2 && wg.shared ? g.L[1] - (g.nt[1] - 1) * RTW : 0;
+  const bool sh = r2 != 0;   // (wave-uniform)
+  const int side2 = sh ? 1 : side, Lb = g.L[side2], l02 = sh ? (g.nt[1] - 1) * RTW : l0;
+  const size_t row_base2 = sh ? (size_t)g.row0[1] + (size_t)n * Lb + l02 : row_base;
+  const int slot2 = sh ? g.tile0[1] + n * g.nt[1] + g.nt[1] - 1 : slot;
+  // tile row r -> (segment, row within it clamped to the segment's valid rows)
+  auto seg_of = [&](int r) { return Seg2 && sh && r >= 16; };
+  auto seg_row = [&](int r) { return seg_of(r) ? min(r - 16, r2 - 1) : min(r, nvalid - 1); };
+  auto x_row = [&](int r) { return (seg_of(r) ? row_base2 : row_base) + seg_row(r); };         // row of x
+  auto pos_row = [&](int r) { return (seg_of(r) ? g.prow0[1] + l02 : g.prow0[side] + l0) + seg_row(r); };   // row of the position table
+  const bool lane_seg = seg_of(col);   // this lane's token (transposed layout: lane = token) is segment 2's
+
   stage_ln_params<THREADS, HAS_B, TAIL>(lnp_s, p, tid);
   // position rows of this tile for the tail (issued early: nothing waits on them yet)
-  const f32x4* pos = reinterpret_cast<const f32x4*>(
-                         p.pos + (size_t)(g.prow0[side] + l0 + min(lrow, nvalid - 1)) * C) + lpart;
+  const f32x4* pos = reinterpret_cast<const f32x4*>(p.pos + (size_t)pos_row(lrow) * C) + lpart;
 
   f32x16 xacc[NMT];  // residual stream of this wave's 32 channels, both row tiles (transposed C layout)
   PHASE_STAMP(p, 0);
@@ -1078,6 +1124,7 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
     // reduce the source image's partial KV states (fixed order): the registers are this head's
     // state in MFMA fragment order (A operand of the transposed apply)
     f32x4 kvB[4];
+    auto reduce_state = [&](f32x4 (&kvB)[4], float* ksum_s, int nts, int src_slot0) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) kvB[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     {
@@ -1111,6 +1158,21 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
       }
       if (tid < C) ksum_s[tid] = ks;
     }
+    };
+    reduce_state(kvB, ksum_s, nts, src_slot0);
+    // (Seg2) segment 2's source image: its own state and Ksum - read only by a shared workgroup, zeros otherwise
+    const int ss2 = p.b_cross ? 1 - side2 : side2;
+    const int S_len2 = g.L[ss2];
+    f32x4 kvB2[4];
+    if constexpr (Seg2) {
+      if (sh) {
+        reduce_state(kvB2, ksum2_s, p.kv_reduced ? 1 : g.nt[ss2], p.kv_reduced ? ss2 * g.N + n : g.tile0[ss2] + n * g.nt[ss2]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) kvB2[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (tid < C) ksum2_s[tid] = 0.f;
+      }
+    }
     ws.template prime<C, P_MERGE, SP::MERGE>(p.b.wmerge, p.b.wmerge_l, wave, 0, lane);
     // phi(Q) of this wave's head for the lane's token, both row tiles: the B fragments of the
     // transposed apply exactly as phase A left them (round 4: FRAGMENT-major phi(Q) buffer,
@@ -1130,7 +1192,7 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
     // before the merge GEMM, the state reduction and the apply run under them)
 #pragma unroll
     for (int mt = 0; mt < NMT; ++mt) {
-      const float* xr = p.x + (row_base + min(32 * mt + col, nvalid - 1)) * C + wcol + 4 * half;
+      const float* xr = p.x + x_row(32 * mt + col) * C + wcol + 4 * half;
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(xr + 8 * g4);
@@ -1146,6 +1208,7 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
     // of `zacc` is that dot): Z needs no LDS pass of its own.  Lane = token t, registers = v.
     {
       f32x4 kvh[2], kvl[2], ksh[2], ksl[2];
+      f32x4 kvh2[2], kvl2[2], ksh2[2], ksl2[2];   // (Seg2: segment 2's state)
       const float inv_S = 1.0f / (float)S_len;
       (void)inv_S;
       if constexpr (gm_f16_range(MODE)) {
@@ -1157,6 +1220,13 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
           const float* kr = ksum_s + wave * HD + 4 * half + 16 * s2;
           split8(*reinterpret_cast<const f32x4*>(kr) * inv_S, *reinterpret_cast<const f32x4*>(kr + 8) * inv_S,
                  ksh[s2], ksl[s2], rg);
+          if constexpr (Seg2) {
+            const float inv_S2 = 1.0f / (float)S_len2;
+            split8(kvB2[2 * s2], kvB2[2 * s2 + 1], kvh2[s2], kvl2[s2], rg);
+            const float* kr2 = ksum2_s + wave * HD + 4 * half + 16 * s2;
+            split8(*reinterpret_cast<const f32x4*>(kr2) * inv_S2, *reinterpret_cast<const f32x4*>(kr2 + 8) * inv_S2,
+                   ksh2[s2], ksl2[s2], rg);
+          }
         }
       }
 #pragma unroll
@@ -1174,6 +1244,20 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
 #pragma unroll
           for (int r = 0; r < 16; ++r) macc[r] = fmaf(c1[r], SPLIT_INV, macc[r]);
           zacc[0] = fmaf(cz[0], SPLIT_INV, zacc[0]);
+          if constexpr (Seg2) {
+            // the same apply against segment 2's state (zeros unless shared), then each lane keeps the product
+            // of its token's segment: a column of the product depends on its own phi(Q) column and the state only
+            f32x16 macc2 = {0}, zacc2 = {0}, c2 = {0}, cz2 = {0};
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+              const f32x4 qh = qfrag[mt][2 * s2], ql = qfrag[mt][2 * s2 + 1];
+              mma16_split3(kvh2[s2], kvl2[s2], qh, ql, macc2, c2);
+              mma16_split3(ksh2[s2], ksl2[s2], qh, ql, zacc2, cz2);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) macc[r] = lane_seg ? fmaf(c2[r], SPLIT_INV, macc2[r]) : macc[r];
+            zacc[0] = lane_seg ? fmaf(cz2[0], SPLIT_INV, zacc2[0]) : zacc[0];
+          }
         } else {
 #pragma unroll
           for (int ks4 = 0; ks4 < 4; ++ks4) {
@@ -1186,8 +1270,9 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
             }
           }
         }
-        const float zdot = gm_f16_range(MODE) ? zacc[0] * (float)S_len : zacc[0];
-        const float zs = (float)S_len / (zdot + ATTN_EPS);
+        const float S_lane = lane_seg ? (float)S_len2 : (float)S_len;   // (Seg2: source tokens of the lane's segment)
+        const float zdot = gm_f16_range(MODE) ? zacc[0] * S_lane : zacc[0];
+        const float zs = S_lane / (zdot + ATTN_EPS);
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4)
           P1.put4(32 * mt + col, wcol + 8 * g4 + 4 * half,
@@ -1305,38 +1390,68 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
 #pragma unroll
     for (int i = 0; i < RTW / 8; ++i) {
       const int r = wave + 8 * i;   // (scalar: a wave-uniform branch, an SGPR row address)
-      if (r < nvalid)
-        store16(p.x + (row_base + r) * C, 16u * (unsigned)lane,
+      if (seg_of(r) ? r - 16 < r2 : r < nvalid)
+        store16(p.x + x_row(r) * C, 16u * (unsigned)lane,
                                     *reinterpret_cast<const f32x4*>(Xf + r * LDA + 4 * lane));
     }
     PHASE_STAMP(p, 8);
     if (TAIL == 2) { range_report<MODE>(rg, p.flags); return; }
   } else {
     if (nchw) {  // first launch, reference layout: transpose on the way in (R2 is free until phase A writes P2)
+      if constexpr (Seg2) {   // each row from its segment's image
+        const int r = tid % RTW;
+        const bool s2 = seg_of(r);
+        const int Ls = s2 ? Lb : L, tok = (s2 ? l02 : l0) + seg_row(r);
+        load_rows_nchw<THREADS, RTW>(R1f, p.feat_nchw[s2 ? 1 : side] + (size_t)n * C * Ls + tok, Ls, tid);
+        load_rows_nchw<THREADS, RTW>(R2f, p.pos_nchw[s2 ? 1 : side] + tok, Ls, tid);
+      } else {
       load_tile_nchw<THREADS, RTW>(R1f, p.feat_nchw[side] + (size_t)n * C * L + l0, L, nvalid, tid);
       load_tile_nchw<THREADS, RTW>(R2f, p.pos_nchw[side] + l0, L, nvalid, tid);
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < (RTW * C / 4) / THREADS; ++i) {  // first launch: x from HBM
         const int idx = tid + THREADS * i;
         const int r = idx >> 6, c4 = idx & 63;
         *reinterpret_cast<f32x4*>(R1f + r * LDA + 4 * c4) =
-            reinterpret_cast<const f32x4*>(p.x + (row_base + min(r, nvalid - 1)) * C)[c4];
+            reinterpret_cast<const f32x4*>(p.x + x_row(r) * C)[c4];
       }
     }
     if (TAIL == 0) ws.template prime<C, P_T0, SP::Q>(p.a.wq, p.a.wq_l, wave, 0, lane);
     if (TAIL == 1) ws.template prime<C, P_T0, SP::DEC_K>(p.d.wk[0], p.d.wk_l[0], wave, 0, lane);
     __syncthreads();
     if (nchw) {  // token-major copies for the later launches (residual reads, position rows)
+      if constexpr (Seg2) {
+#pragma unroll
+        for (int i = 0; i < 32 / 8; ++i) {   // (a one-row-tile workgroup: rows 0..31, a row per wave and pass)
+          const int r = wave + 8 * i;
+          if (seg_of(r) ? r - 16 < r2 : r < nvalid) {
+            reinterpret_cast<f32x4*>(p.x + x_row(r) * C)[lane] = *reinterpret_cast<const f32x4*>(R1f + r * LDA + 4 * lane);
+            if (n == 0)
+              reinterpret_cast<f32x4*>(p.pos_out + (size_t)pos_row(r) * C)[lane] = *reinterpret_cast<const f32x4*>(R2f + r * LDA + 4 * lane);
+          }
+        }
+      } else {
       store_tile_tokens<THREADS, RTW>(p.x + row_base * C, R1f, nvalid, tid);
       if (n == 0) store_tile_tokens<THREADS, RTW>(p.pos_out + (size_t)(g.prow0[side] + l0) * C, R2f, nvalid, tid);
+      }
     }
     PHASE_STAMP(p, 14);   // (first launch: input tile in LDS - transposed from NCHW - and stored token-major)
   }
 
   // (MASKED: the tile's mask values go where the LayerNorm exchange buffer was - dead after phase B;
   //  two barriers lie between this store and the first read)
-  if constexpr (MASKED && TAIL != 2) {
+  if constexpr (MASKED && TAIL != 2 && Seg2) {
+    // a one-row-tile workgroup: a mask vector per segment - [0, 32) segment 1's rows, [32, 64) segment 2's, each 0
+    // on the other segment's rows and past its own end (the row masks of the two states)
+    if (tid < 32) {
+      const bool s2 = seg_of(tid);
+      const bool ok = s2 ? tid - 16 < r2 : tid < nvalid;
+      const float m = ok ? p.mask[s2 ? 1 : side][(size_t)n * (s2 ? Lb : L) + (s2 ? l02 : l0) + seg_row(tid)] : 0.f;
+      lnx_s[tid] = s2 ? 0.f : m;
+      lnx_s[32 + tid] = s2 ? m : 0.f;
+    }
+  } else if constexpr (MASKED && TAIL != 2) {
     if (tid < RTW) lnx_s[tid] = tid < nvalid ? p.mask[side][(size_t)n * L + l0 + tid] : 0.f;
   }
   if (TAIL == 0) {
@@ -1395,7 +1510,7 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
         if constexpr (NMT == 1 && CI % 2 == 1) return;
         if (mt == 1 && !two) return;   // (rows 32.. of a one-row-tile workgroup are never read)
         // (MASKED: q_mask of the lane's token, from the tile's mask values in LDS)
-        const float qmask = MASKED ? lnx_s[32 * mt + col] : 1.0f;
+        const float qmask = MASKED ? lnx_s[32 * (Seg2 ? (int)lane_seg : mt) + col] : 1.0f;
         const float a = MASKED ? elu1(accQ[mt][2 * pr]) * qmask : elu1(accQ[mt][2 * pr]);
         const float b = MASKED ? elu1(accQ[mt][2 * pr + 1]) * qmask : elu1(accQ[mt][2 * pr + 1]);
         if constexpr (MODE == GM_BF16) {   // the bf16 build's apply takes f32 fragments: k-group = register quad
@@ -1427,6 +1542,13 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
     float ksum;
     kv_state_64<MODE, NMT, MASKED>(accK, accV, L, nvalid, half, ws.two(), kv, ksum, rg, lnx_s);
     kv_state_write(kv, ksum, lane, wave, p.kv_out, p.ks_out, slot);
+    if constexpr (Seg2) {
+      // segment 2's state -> image 2's last partial slot.  Its rows sit in k16 step 1 (tokens 16..31) where the
+      // tile of its own had them in step 0: the same products in the same k-slots one step later, exact zeros in
+      // the other step - bit for bit the state (and Ksum) that tile wrote
+      kv_state_64<MODE, NMT, MASKED, true>(accK, accV, Lb, 16 + r2, half, false, kv, ksum, rg, lnx_s + 32);
+      if (sh) kv_state_write(kv, ksum, lane, wave, p.kv_out, p.ks_out, slot2);
+    }
     PHASE_STAMP(p, 12);
     // (the LayerNorm exchange buffer is dead after phase B)
   } else if (TAIL == 1) {
@@ -1466,12 +1588,13 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
                                                    nullptr, 0, 0);
       f32x16 kv;
       float ksum;
-      kv_state_64<MODE, NMT, MASKED>(accK, accV, L, nvalid, half, ws.two(), kv, ksum, rg, lnx_s);
+      // the state of one segment -> the partials of its image's tile slot (`on`: wave-uniform, false = nothing stored)
+      auto emit = [&](int side_, int slot_, bool on) {
       if constexpr (dl == 1) {
-        kv_state_write(kv, ksum, lane, wave, p.dkv1_out, p.dks1_out, slot);
+        if (on) kv_state_write(kv, ksum, lane, wave, p.dkv1_out, p.dks1_out, slot_);
       } else {
         // partial message / normaliser of decoder layer 0's cross-attention (see k_encoder)
-        const float* q0 = p.dec_q0 + side * C + wave * HD;
+        const float* q0 = p.dec_q0 + side_ * C + wave * HD;
         float a = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) a += q0[crow(r, half)] * kv[r];
@@ -1482,10 +1605,17 @@ __device__ __forceinline__ void encoder64_body(const EncLaunch& p, float* smem) 
         z += __shfl_xor(z, 4, 64);
         z += __shfl_xor(z, 8, 64);
         z += __shfl_xor(z, 16, 64);
-        if (half == 0) p.att0_out[(size_t)slot * C + wave * HD + col] = a;
-        if (lane == 0) p.z0_out[(size_t)slot * NH + wave] = z;
-        ws.template prime<C, P_T2, SP::DEC_K>(p.d.wk[1], p.d.wk_l[1], wave, 0, lane);
+        if (on && half == 0) p.att0_out[(size_t)slot_ * C + wave * HD + col] = a;
+        if (on && lane == 0) p.z0_out[(size_t)slot_ * NH + wave] = z;
       }
+      };
+      kv_state_64<MODE, NMT, MASKED>(accK, accV, L, nvalid, half, ws.two(), kv, ksum, rg, lnx_s);
+      emit(side, slot, true);
+      if constexpr (Seg2) {   // segment 2 (see phase A): image 2's own query, its own slot
+        kv_state_64<MODE, NMT, MASKED, true>(accK, accV, Lb, 16 + r2, half, false, kv, ksum, rg, lnx_s + 32);
+        emit(side2, slot2, sh);
+      }
+      if constexpr (dl == 0) ws.template prime<C, P_T2, SP::DEC_K>(p.d.wk[1], p.d.wk_l[1], wave, 0, lane);
     };
     dec_layer(std::integral_constant<int, 0>{});
     dec_layer(std::integral_constant<int, 1>{});
@@ -1500,13 +1630,9 @@ __global__ __launch_bounds__(512) void k_encoder64(EncLaunch p) {
     // split mode: the row-tile count is a compile-time property of the body (branch-free GEMM
     // steps, which is what lets hipcc interleave the epilogue slices with the MFMAs), chosen
     // per workgroup - a workgroup-uniform branch at the top instead of one around every MFMA
-    const Geom& g = p.g;
-    const int logical = xcd_remap(blockIdx.x, g.ntiles);
-    const int per = g.nt[0] + g.nt[1];
-    const int rem = logical - (logical / per) * per;
-    const int side = rem >= g.nt[0];
-    const int t_idx = side ? rem - g.nt[0] : rem;
-    const int nvalid = min(RT, g.L[side] - t_idx * RT);
+    // (a shared workgroup - two ragged last tiles - is image 1's last tile here: at most 16 rows, the one-row-tile body)
+    const EncWg wg = enc_wg(p);
+    const int nvalid = min(RT, p.g.L[wg.side] - wg.t_idx * RT);
     if (__builtin_amdgcn_readfirstlane(nvalid > 32 ? 1 : 0)) encoder64_body<HAS_B, TAIL, MODE, POL, 2, RT, MASKED>(p, smem);
     else encoder64_body<HAS_B, TAIL, MODE, POL, 1, RT, MASKED>(p, smem);
   } else {
@@ -1546,11 +1672,26 @@ static hipError_t launch_b_tail(bool has_b, int tail, F launch) {
   return hipGetLastError();
 }
 
+// Tail sharing (EncLaunch::tail_share as the caller sets it: 0 = off, else wanted): taken by k_encoder64 in the
+// two-plane modes with linear attention when both images end in a ragged tile of 1..16 rows - the two tails then fit
+// the two 16-row halves of one 32-row MFMA tile (encoder64_body: Seg2), one workgroup per pair fewer.
+static bool encoder_tail_share(const EncLaunch& p, int mode) {
+  if (!p.tail_share || mode != GM_SPLIT || p.tile_rows != RT || p.attn_full) return false;
+  const int r1 = p.g.L[0] % RT, r2 = p.g.L[1] % RT;
+  return r1 >= 1 && r1 <= 16 && r2 >= 1 && r2 <= 16;
+}
+int encoder_workgroups(const EncLaunch& p, int mode) {
+  return p.g.ntiles - (encoder_tail_share(p, mode) ? p.g.N : 0);
+}
+
 // Which kernel runs: guards first, then one line per kernel (template arguments after MODE: see each kernel;
 // b() / t() are the tags' values).  DESIGN.md 3.2 lists every instantiation and the setting that selects it.
 template <int MODE>
-static hipError_t launch_encoder_mode(const EncLaunch& p, bool has_b, int tail, hipStream_t s) {
-  const dim3 grid(p.g.ntiles);
+static hipError_t launch_encoder_mode(const EncLaunch& p_in, bool has_b, int tail, hipStream_t s) {
+  EncLaunch p = p_in;
+  p.tail_share = encoder_tail_share(p_in, MODE) ? 1 : 0;
+  p.nwg = encoder_workgroups(p_in, MODE);
+  const dim3 grid(p.nwg);
   if (p.mask[0] || p.mask[1]) {
     // forward_dummy's masks: built for the two-plane arithmetic (every site fp32-class, or the
     // precision policy), linear attention, both tile sizes

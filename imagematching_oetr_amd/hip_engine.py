@@ -102,6 +102,8 @@ EXPORTS = (
     'oetr_linear_attention_masked', 'oetr_debug_decoder_fault',
     'oetr_flagslot_device_pointer', 'oetr_forward_flagslot', 'oetr_forward_tokens_flagslot',
     'oetr_neck_forward_tokens_status', 'oetr_debug_mfma_rate')
+# The tail-sharing switch (include/oetr_tail_share.h): an extension header like the ones below, no version of its own
+TAIL_SHARE_EXPORTS = ('oetr_set_tail_share', 'oetr_debug_encoder_grid')
 
 FLAG_F16_RANGE = 1   # OETR_FLAG_F16_RANGE
 FLAG_EXCHANGE = 2    # OETR_FLAG_EXCHANGE: the split decoder's workgroups were not resident together
@@ -264,6 +266,10 @@ def load_library(path=None):
     lib.oetr_set_attention.argtypes = [vp, i]
     lib.oetr_set_state_prereduce.restype = i
     lib.oetr_set_state_prereduce.argtypes = [vp, i]
+    lib.oetr_set_tail_share.restype = i
+    lib.oetr_set_tail_share.argtypes = [vp, i]
+    lib.oetr_debug_encoder_grid.restype = i
+    lib.oetr_debug_encoder_grid.argtypes = [vp]
     lib.oetr_set_tail_mode.restype = i
     lib.oetr_set_tail_mode.argtypes = [vp, i]
     lib.oetr_set_decoder_split.restype = i
@@ -725,6 +731,16 @@ class HotPathEngine:
         launch from 768 source tokens per image), 0 off, 1 in a launch of their own (bit-identical
         results in every setting)."""
         _check(self.lib, self.lib.oetr_set_state_prereduce(self._h, int(mode)), 'oetr_set_state_prereduce')
+
+    def set_tail_share(self, mode):
+        """``oetr_set_tail_share``: an image pair's two ragged last token tiles (1..16 rows each, 64-row
+        encoder workgroups) in one workgroup - -1 automatic (the library default: wherever the shape allows
+        it), 0 off (bit-identical results in both settings)."""
+        _check(self.lib, self.lib.oetr_set_tail_share(self._h, int(mode)), 'oetr_set_tail_share')
+
+    def debug_encoder_grid(self):
+        """``oetr_debug_encoder_grid`` (tests): workgroups of each encoder launch of the most recent call."""
+        return int(self.lib.oetr_debug_encoder_grid(self._h))
 
     def set_tail_mode(self, mode):
         """``oetr_set_tail_mode``: order of the forward path's tail - 0 automatic (the default), 1
