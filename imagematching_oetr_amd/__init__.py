@@ -27,6 +27,8 @@ from .evaluate import evaluate_dummy, evaluate_indexed, keypoint_repeatability, 
 from .match_score import match_params, score_matches  # noqa: F401
 from .keypoint_score import ground_truth_matches, score_keypoints  # noqa: F401
 from .match_assembly import assemble_matches, few_match_pairs  # noqa: F401
+from .homography import (homography_accuracy, homography_params, overlap_boxes_from_homography,  # noqa: F401
+                         rescale_homography, score_matches_homography)
 from .reader import overlap_frame, read_overlap_images  # noqa: F401
 from .hip_engine import (FLAG_EXCHANGE, FLAG_F16_RANGE, FLAG_INDEX, FLAG_INVALID, FULL_ATTENTION_VARIANTS, HotPathEngine, KernelTrace, NeckEngine, OetrError,  # noqa: F401
                          OetrExchangeError, OetrRangeError,
@@ -42,4 +44,6 @@ __all__ = ['Cfg', 'get_cfg_defaults', 'OETR', 'build_detectors',
            'crop_pair_table', 'overlap_crop_batch', 'OverlapCropBatch', 'keypoints_to_origin', 'crop_pairs',
            'score_matches', 'match_params', 'match_precision',
            'score_keypoints', 'keypoint_repeatability', 'ground_truth_matches',
-           'assemble_matches', 'few_match_pairs']
+           'assemble_matches', 'few_match_pairs',
+           'homography_params', 'rescale_homography', 'score_matches_homography', 'homography_accuracy',
+           'overlap_boxes_from_homography']

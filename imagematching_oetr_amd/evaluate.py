@@ -8,7 +8,8 @@ included, as in the reference - and the recall at a threshold is the share of va
 
 The ground truth comes from the batch (``overlap_box1`` / ``overlap_box2``, what the reference's
 dataset emits) or is computed on the device from depth maps, intrinsics and poses
-(``covis.overlap_boxes_from_batch``).  ``evaluate_indexed`` scores the feature-bank route the same
+(``covis.overlap_boxes_from_batch``) or from a homography
+(``homography.overlap_boxes_from_homography``).  ``evaluate_indexed`` scores the feature-bank route the same
 way: a pair list over an image set, the ground truth by index from a ``covis_set.DepthSet``.
 ``match_precision`` summarises ``match_score.score_matches``: the reference's ``validation_error``
 precision per pair, from one read of the counters.  ``keypoint_repeatability`` summarises
@@ -19,6 +20,7 @@ import torch
 
 from .covis import overlap_boxes_from_batch
 from .covis_set import overlap_boxes_indexed
+from .homography import overlap_boxes_from_homography
 from .losses import bbox_iou_aligned, bbox_oiou
 from .pipeline import _model_device, forward_pairs_indexed
 
@@ -66,12 +68,15 @@ def evaluate_dummy(model, batches, iou_thrs=DEFAULT_IOU_THRS, oiou=False, gt='au
     """``batches``: an iterable of dataset-style dicts with ``image1`` / ``image2`` ``[N,H,W,3]`` in
     [0,1] and the ground truth: ``overlap_box1`` / ``overlap_box2`` ``[N,4]`` (``gt='batch'``), or
     ``depth1``, ``intrinsics1``, ``pose1``, ``bbox1``, ``ratio1`` and the same for ``2`` (``gt='depth'``:
-    the boxes are computed on the device).  ``gt='auto'`` takes the batch's boxes where it has them.
+    the boxes are computed on the device), or ``homography`` ``[N,3,3]`` (``gt='homography'``: the
+    homography from ``image1`` to ``image2`` in the frame of the two images AS GIVEN, pixel centres at
+    integer coordinates; the boxes are ``homography.overlap_boxes_from_homography``'s, computed on the
+    device).  ``gt='auto'`` takes the batch's boxes where it has them, else the depth route.
 
     Returns ``{'recalls': ndarray[len(iou_thrs)], 'n': number of scored boxes (2 per pair),
     'mean_iou': float (a NaN score - ``oiou`` against a zero box - counts as 0, as it fails every
     threshold), 'n_valid_pairs': int}`` - pairs whose ground truth is valid: ``overlap_valid``
-    where the ground truth carries it (always for ``gt='depth'``), otherwise pairs with a non-zero
+    where the ground truth carries it (always for ``gt='depth'`` and ``gt='homography'``), otherwise pairs with a non-zero
     ground-truth box.  With a ``logger`` the reference's table (R0.5, R0.75, R0.9: entries 0, 5, 8 of
     the default thresholds) is logged.
 
@@ -80,8 +85,8 @@ def evaluate_dummy(model, batches, iou_thrs=DEFAULT_IOU_THRS, oiou=False, gt='au
     tensors are kept and scored after one ``model.hip_flush()`` at the end, as
     ``pipeline.forward_pairs_raw`` does.  IoUs and the per-threshold counts stay on the device; the
     whole evaluation reads the device once."""
-    if gt not in ('auto', 'batch', 'depth'):
-        raise ValueError(f"gt must be 'auto', 'batch' or 'depth', got {gt!r}")
+    if gt not in ('auto', 'batch', 'depth', 'homography'):
+        raise ValueError(f"gt must be 'auto', 'batch', 'depth' or 'homography', got {gt!r}")
     thrs = np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
     device = _model_device(model)
     produced = []          # (gt_box1, gt_box2, valid or None, pred_box1, pred_box2) per batch
@@ -92,7 +97,12 @@ def evaluate_dummy(model, batches, iou_thrs=DEFAULT_IOU_THRS, oiou=False, gt='au
         has_boxes = 'overlap_box1' in batch and 'overlap_box2' in batch
         if gt == 'batch' and not has_boxes:
             raise KeyError("gt='batch': the batch has no overlap_box1 / overlap_box2")
-        if gt == 'depth' or not has_boxes:
+        if gt == 'homography':
+            if 'homography' not in batch:
+                raise KeyError("gt='homography': the batch has no homography")
+            truth = overlap_boxes_from_homography(batch['homography'], size1=tuple(image1.shape[1:3]),
+                                                  size2=tuple(image2.shape[1:3]))
+        elif gt == 'depth' or not has_boxes:
             truth = overlap_boxes_from_batch(batch)
         else:
             truth = batch

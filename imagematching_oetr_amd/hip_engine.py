@@ -149,6 +149,13 @@ MATCH_ASSEMBLY_EXPORTS = ('oetr_match_assembly_abi_version', 'oetr_match_assembl
                           'oetr_assemble_matches')
 MATCH_ASSEMBLY_COUNTERS = 4         # OETR_MATCH_ASSEMBLY_COUNTERS
 
+# The homography extension (include/oetr_homography.h): likewise
+HOMOGRAPHY_ABI_VERSION = 1
+HOMOGRAPHY_EXPORTS = ('oetr_homography_abi_version', 'oetr_homography_match_score', 'oetr_homography_workspace_bytes',
+                      'oetr_homography_boxes')
+HOMOGRAPHY_PARAM_DOUBLES = 16       # OETR_HOMOGRAPHY_PARAM_DOUBLES
+HOMOGRAPHY_MAX_THRESHOLDS = 16      # OETR_HOMOGRAPHY_MAX_THRESHOLDS
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -404,6 +411,20 @@ def load_library(path=None):
     if lib.oetr_match_assembly_abi_version() != MATCH_ASSEMBLY_ABI_VERSION:
         raise RuntimeError(f'{p}: match-assembly ABI version {lib.oetr_match_assembly_abi_version()} != '
                            f'{MATCH_ASSEMBLY_ABI_VERSION}')
+    # include/oetr_homography.h
+    lib.oetr_homography_abi_version.restype = i
+    lib.oetr_homography_abi_version.argtypes = []
+    lib.oetr_homography_match_score.restype = i
+    # params, offsets, n_pairs, k1, k2, n_matches, thresholds (host), n_thresholds, dist_sq, counts, stream
+    lib.oetr_homography_match_score.argtypes = [vp, vp, i, vp, vp, C.c_int64, C.POINTER(C.c_double), i, vp, vp, vp]
+    lib.oetr_homography_workspace_bytes.restype = sz
+    lib.oetr_homography_workspace_bytes.argtypes = [i]
+    lib.oetr_homography_boxes.restype = i
+    # params, n_pairs, max_h1, max_w1, workspace, workspace_bytes, box1, box2, valid, count, stream
+    lib.oetr_homography_boxes.argtypes = [vp, i, i, i, vp, sz] + [vp] * 5
+    if lib.oetr_homography_abi_version() != HOMOGRAPHY_ABI_VERSION:
+        raise RuntimeError(f'{p}: homography ABI version {lib.oetr_homography_abi_version()} != '
+                           f'{HOMOGRAPHY_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
