@@ -14,6 +14,8 @@ way: a pair list over an image set, the ground truth by index from a ``covis_set
 ``match_precision`` summarises ``match_score.score_matches``: the reference's ``validation_error``
 precision per pair, from one read of the counters.  ``keypoint_repeatability`` summarises
 ``keypoint_score.score_keypoints`` the same way: the reference's repeatability per pair and threshold.
+``pose_errors`` / ``pose_auc`` / ``match_pose_auc`` summarise ``pose_ransac.estimate_poses``: the reference's
+``compute_pose_error`` per pair and its AUC of the pose error.
 """
 import numpy as np
 import torch
@@ -203,3 +205,61 @@ def keypoint_repeatability(result):
     return {'repeatability': per_pair, 'mean_repeatability': mean, 'thresholds': thresholds,
             'n_pairs': int(scored.sum()), 'n_not_scored': int((~scored).sum()),
             'n_keypoints': int(counts[scored, :, 0].sum()), 'n_kept': int(counts[scored, :, 1].sum())}
+
+
+def pose_errors(result):
+    """The reference's ``compute_pose_error`` (``dloc/evaluate/utils/evaluation.py``: ``angle_error_mat``,
+    ``angle_error_vec``) of a ``pose_ransac.estimate_poses`` result, from ONE device read of its
+    ``cosines`` and ``counts``: the cosines clipped to +-1, ``arccos`` - the one transcendental of the
+    route, left to the host - in degrees, ``err_t = min(e, 180 - e)``.  A pair without a pose (selected
+    model -1, or cosines that are not finite) gives ``inf``, as ``validation_error`` does.
+
+    Returns ``{'err_R', 'err_t', 'pose_error': float64 [P]}`` with ``pose_error = max(err_t, err_R)`` as
+    ``eval_megadepth.py`` forms it."""
+    cos, counts = result['cosines'], result['counts']
+    if torch.is_tensor(cos):
+        # both in ONE float64 tensor (exact for these integers): one read
+        packed = torch.cat([cos.reshape(-1, 2), counts.reshape(-1, 5).to(torch.float64)], 1).cpu().numpy()
+        cos, counts = packed[:, :2], packed[:, 2:]
+    cos, counts = np.asarray(cos, np.float64).reshape(-1, 2), np.asarray(counts).reshape(-1, 5)
+    none = ~np.isfinite(cos).all(1) | (counts[:, 2] < 0)
+    with np.errstate(all='ignore'):
+        c = np.clip(np.where(none[:, None], 1.0, cos), -1.0, 1.0)
+        err_R = np.rad2deg(np.abs(np.arccos(c[:, 0])))
+        e = np.rad2deg(np.arccos(c[:, 1]))
+        err_t = np.minimum(e, 180 - e)
+    err_R, err_t = np.where(none, np.inf, err_R), np.where(none, np.inf, err_t)
+    return {'err_R': err_R, 'err_t': err_t, 'pose_error': np.maximum(err_t, err_R)}
+
+
+def pose_auc(errors, thresholds=(5, 10, 20)):
+    """The area under the recall curve of the pose errors up to each threshold, over the threshold - what
+    the reference's ``pose_auc`` (``dloc/evaluate/utils/utils.py``) computes.  The curve rises from (0, 0)
+    through ``(e_i, i / n)`` for the errors in ascending order (degrees; ``inf`` for a pair without a pose);
+    the ``k`` errors strictly below a threshold ``t`` each close one trapezoid, and a flat piece at ``k / n``
+    runs from the last of them to ``t``.  ``errors``: an array, or the dict :func:`pose_errors` returns.
+    -> a list, one value in [0, 1] per threshold; NaN for no pairs."""
+    errors = errors['pose_error'] if isinstance(errors, dict) else errors
+    ascending = np.sort(np.asarray(errors, np.float64).reshape(-1))
+    n = len(ascending)
+    if n == 0:
+        return [float('nan') for _ in thresholds]
+    aucs = []
+    for t in thresholds:
+        below = int(np.count_nonzero(ascending < t))
+        area, at_e, at_r = 0.0, 0.0, 0.0
+        for i in range(below):                            # added in ascending order
+            share = (i + 1) / n
+            area = area + (ascending[i] - at_e) * (share + at_r) / 2.0
+            at_e, at_r = ascending[i], share
+        area = area + (t - at_e) * (at_r + at_r) / 2.0
+        aucs.append(float(area / t))
+    return aucs
+
+
+def match_pose_auc(result, thresholds=(5, 10, 20)):
+    """:func:`pose_errors` and :func:`pose_auc` together, times 100, as ``eval_megadepth.py`` prints it:
+    ``{'auc': [AUC@5, AUC@10, AUC@20], 'thresholds', 'pose_error', 'err_R', 'err_t', 'n_pairs', 'n_no_pose'}``."""
+    errs = pose_errors(result)
+    return {'auc': [100.0 * a for a in pose_auc(errs['pose_error'], thresholds)], 'thresholds': tuple(thresholds),
+            'n_pairs': int(errs['pose_error'].size), 'n_no_pose': int(np.isinf(errs['pose_error']).sum()), **errs}

@@ -156,6 +156,14 @@ HOMOGRAPHY_EXPORTS = ('oetr_homography_abi_version', 'oetr_homography_match_scor
 HOMOGRAPHY_PARAM_DOUBLES = 16       # OETR_HOMOGRAPHY_PARAM_DOUBLES
 HOMOGRAPHY_MAX_THRESHOLDS = 16      # OETR_HOMOGRAPHY_MAX_THRESHOLDS
 
+# The relative-pose extension (include/oetr_pose_ransac.h): likewise
+POSE_RANSAC_ABI_VERSION = 1
+POSE_RANSAC_EXPORTS = ('oetr_pose_ransac_abi_version', 'oetr_pose_ransac_workspace_bytes', 'oetr_pose_ransac',
+                       'oetr_pose_ransac_sqrt')
+POSE_RANSAC_MAX_HYPOTHESES = 4096   # OETR_POSE_RANSAC_MAX_HYPOTHESES
+POSE_RANSAC_MAX_MODELS = 12288      # OETR_POSE_RANSAC_MAX_MODELS
+POSE_RANSAC_COUNTERS = 5            # OETR_POSE_RANSAC_COUNTERS
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -425,6 +433,20 @@ def load_library(path=None):
     if lib.oetr_homography_abi_version() != HOMOGRAPHY_ABI_VERSION:
         raise RuntimeError(f'{p}: homography ABI version {lib.oetr_homography_abi_version()} != '
                            f'{HOMOGRAPHY_ABI_VERSION}')
+    # include/oetr_pose_ransac.h
+    lib.oetr_pose_ransac_abi_version.restype = i
+    lib.oetr_pose_ransac_abi_version.argtypes = []
+    lib.oetr_pose_ransac_workspace_bytes.restype = sz
+    lib.oetr_pose_ransac_workspace_bytes.argtypes = [i, i]
+    lib.oetr_pose_ransac.restype = i
+    # params, offsets, pair_ids, n_pairs, k1, k2, n_matches, n_hyp, seed, px_thr, models_in, n_models_in, workspace,
+    # workspace_bytes, model, pose, cosines, counts, inliers, stream
+    lib.oetr_pose_ransac.argtypes = [vp, vp, vp, i, vp, vp, C.c_int64, i, C.c_uint32, C.c_double, vp, i, vp, sz] + [vp] * 6
+    lib.oetr_pose_ransac_sqrt.restype = i
+    lib.oetr_pose_ransac_sqrt.argtypes = [vp, vp, C.c_int64, vp]
+    if lib.oetr_pose_ransac_abi_version() != POSE_RANSAC_ABI_VERSION:
+        raise RuntimeError(f'{p}: pose-ransac ABI version {lib.oetr_pose_ransac_abi_version()} != '
+                           f'{POSE_RANSAC_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
