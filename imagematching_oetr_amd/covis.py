@@ -14,6 +14,7 @@ import ctypes as C
 import torch
 
 from . import hip_engine
+from ._inputs import _device_of
 from .hip_engine import COVIS_PARAM_DOUBLES, _check, _stream
 
 _SIDES = ('depth', 'intrinsics', 'pose', 'bbox', 'ratio')
@@ -79,16 +80,6 @@ def covis_boxes(depth1, depth2, params, masks=False, out=None):
     return out
 
 
-def _target_device(tensors):
-    for t in tensors:
-        if torch.is_tensor(t) and t.is_cuda:
-            return t.device
-    if not torch.cuda.is_available():
-        raise RuntimeError('overlap_boxes_from_depth needs a GPU (HIP) device: the inputs are on the CPU and no '
-                           'GPU is present. There is no CPU implementation.')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
 @torch.no_grad()
 def overlap_boxes_from_depth(depth1, intrinsics1, pose1, bbox1, ratio1, depth2, intrinsics2, pose2, bbox2, ratio2,
                              masks=False, stream=None):
@@ -112,7 +103,7 @@ def overlap_boxes_from_depth(depth1, intrinsics1, pose1, bbox1, ratio1, depth2, 
     the current one).  Parity with the reference holds for square maps; for ``H != W`` the landing
     test is ``i < W, j < H`` where the reference compares with the other side
     (``include/oetr_covis.h``).  Without a GPU this raises ``RuntimeError``."""
-    dev = _target_device((depth1, depth2, pose1, pose2, intrinsics1, intrinsics2))
+    dev = _device_of('overlap_boxes_from_depth', (depth1, depth2, pose1, pose2, intrinsics1, intrinsics2))
     d1, d2 = torch.as_tensor(depth1), torch.as_tensor(depth2)
     if d1.dim() != 3 or d1.shape != d2.shape:
         raise ValueError(f'depth1 / depth2 must be [N,H,W] of one shape, got {tuple(d1.shape)} / {tuple(d2.shape)}')

@@ -17,7 +17,7 @@ import ctypes as C
 import torch
 
 from . import hip_engine
-from ._inputs import _pair_tensor
+from ._inputs import _pair_tensor, _workspace
 from .hip_engine import COVIS_MAX_SIDE, COVIS_PARAM_DOUBLES, _check, _CovisMap, _stream
 
 # One image's float64 record, 45 values: pose [0:16], inverse(pose) [16:32], K [32:41], bbox [41:43], ratio [43:45]
@@ -165,10 +165,7 @@ def covis_boxes_indexed(table, n_maps, max_pixels, idx1, idx2, params, out=None)
     if n == 0:
         return out
     lib = hip_engine.load_library()
-    need = int(lib.oetr_covis_set_workspace_bytes(n))
-    workspace = out.get('workspace')
-    if workspace is None or workspace.numel() < need:
-        workspace = out['workspace'] = torch.empty(need, dtype=torch.uint8, device=dev)
+    workspace = _workspace(out, int(lib.oetr_covis_set_workspace_bytes(n)), dev)
     with torch.cuda.device(dev):
         _check(lib, lib.oetr_covis_boxes_indexed(
             table.data_ptr(), int(n_maps), idx1.data_ptr(), idx2.data_ptr(), params.data_ptr(), n, int(max_pixels),

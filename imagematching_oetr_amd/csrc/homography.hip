@@ -3,11 +3,10 @@
 // its own in the order and with the parentheses written there (no contraction into FMAs: rint() and the "<=" tests
 // are discontinuous and the parity target is a float64 numpy program), IEEE division.
 //
-// k_homography_score: one thread per match row, 256-thread workgroups, the row -> list rule and the wave-level
-// structure of k_match_score (match_score.hip).  The list of the wave's FIRST row is searched once per wave with
-// scalar loads; a wave whose rows all lie in that list - the common case - takes the nine doubles of H by scalar
-// loads too, so a row's vector loads are its two keypoints.  Per row 6 v_mul_f64, 9 v_add_f64 and two divisions.  The
-// squared thresholds travel in the kernel's arguments.  Counters: a wave whose counted rows all belong to one pair
+// k_homography_score: one thread per match row, 256-thread workgroups, the row -> list step of match_list.h.  A wave
+// whose rows all lie in the list of its first row - the common case - takes the nine doubles of H by scalar loads,
+// as it took that list, so a row's vector loads are its two keypoints.  Per row 6 v_mul_f64, 9 v_add_f64 and two
+// divisions.  The squared thresholds travel in the kernel's arguments.  Counters: a wave whose counted rows all belong to one pair
 // takes one ballot and one popcount per threshold, lane t keeping threshold t's count, and issues ONE atomic
 // instruction on the pair's adjacent counters (one instruction per threshold, all from lane 0, cost twice the whole
 // call; summing the workgroup's four waves through LDS first, and 8-byte keypoint loads, gained nothing measurable:
@@ -27,6 +26,7 @@
 
 #include "../../include/oetr_homography.h"
 #include "common.h"
+#include "match_list.h"
 
 namespace oetr {
 
@@ -43,17 +43,6 @@ enum { B_MINU, B_MINV, B_MAXU, B_MAXV, B_MINI, B_MINJ, B_MAXI, B_MAXJ, B_COUNT, 
 struct HomThresholds {
   double sq[HOM_MAX_THR];                                        // thr * thr, NaN past n_thresholds
 };
-
-// The largest p in [0, n_pairs) with offsets[p] <= m, or -1 (the offsets are assumed non-decreasing).  Reads
-// offsets[0 .. n_pairs-1] only.
-__device__ __forceinline__ int hom_find_list(const int32_t* __restrict__ offsets, int n_pairs, int m) {
-  int lo = 0, hi = n_pairs;
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);     // lo <= mid < hi <= n_pairs
-    if (offsets[mid] <= m) lo = mid + 1; else hi = mid;
-  }
-  return lo - 1;
-}
 
 // One row of tests/homography_oracle.py::score under the H at P.  The one copy of the arithmetic; inlined twice (H by
 // scalar loads / by per-lane loads).
@@ -81,22 +70,8 @@ __global__ __launch_bounds__(HOM_THREADS) void k_homography_score(
     x = k1[at], y = k1[at + 1], x2 = k2[at], y2 = k2[at + 1];
   }
 
-  // the list of the wave's first row, by scalar loads (k_match_score has the argument for the later rows)
-  const int64_t row0 = (int64_t)blockIdx.x * HOM_THREADS + (int64_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x);
-  int p0 = -1, end0 = 0;
-  if (row0 < (int64_t)n_matches) {
-    p0 = __builtin_amdgcn_readfirstlane(hom_find_list(offsets, n_pairs, (int)row0));
-    if (p0 >= 0) end0 = offsets[p0 + 1];                            // p0 + 1 <= n_pairs
-  }
-  int p = -1;
-  if (active) {
-    if (p0 >= 0 && m < end0) {
-      p = p0;
-    } else {
-      p = hom_find_list(offsets, n_pairs, m);
-      if (p >= 0 && !(m < offsets[p + 1])) p = -1;
-    }
-  }
+  int p0, p;                                                        // the wave's first row's list, this row's
+  wave_find_list<HOM_THREADS>(offsets, n_pairs, n_matches, active, m, p0, p);
 
   double d = __longlong_as_double(0x7ff8000000000000ll);
   if (__ballot(active && p != p0) == 0ull) {
@@ -115,11 +90,9 @@ __global__ __launch_bounds__(HOM_THREADS) void k_homography_score(
     if (t < n_thr && counted >= 0 && d <= thr.sq[t]) hits |= 1u << t;
 
   const int stride = 1 + n_thr;
-  const unsigned long long counting = __ballot(counted >= 0);
-  if (counting == 0ull) return;                                     // wave-uniform
-  const int first = __shfl(counted, __ffsll((long long)counting) - 1, 64);
-  const bool one_pair = __ballot(counted >= 0 && counted != first) == 0ull;
-  if (one_pair) {
+  const WaveCounted w = wave_counted(counted);
+  if (!w.any) return;                                               // wave-uniform
+  if (w.one_pair) {
     // lane t keeps the wave's count of threshold t: ONE atomic instruction per wave, on adjacent counters
     const int lane = threadIdx.x & 63;
     int mine = 0;
@@ -130,7 +103,7 @@ __global__ __launch_bounds__(HOM_THREADS) void k_homography_score(
         if (lane == t) mine = n;
       }
     }
-    if (mine) atomicAdd(counts + (size_t)first * stride + 1 + lane, mine);     // mine != 0 only for lane < n_thr
+    if (mine) atomicAdd(counts + (size_t)w.first * stride + 1 + lane, mine);   // mine != 0 only for lane < n_thr
   } else if (counted >= 0) {
     int32_t* c = counts + (size_t)counted * stride;
     for (int t = 0; t < n_thr; ++t)
@@ -144,13 +117,7 @@ __global__ void k_homography_init(const int32_t* __restrict__ offsets, int n_pai
   const unsigned at = blockIdx.x * blockDim.x + threadIdx.x;
   if (at >= (unsigned)(n_pairs * stride)) return;                   // n_pairs * stride <= INT32_MAX (host check)
   const int p = (int)(at / (unsigned)stride), k = (int)(at - (unsigned)p * (unsigned)stride);
-  int32_t v = 0;
-  if (k == 0) {
-    long long len = (long long)offsets[p + 1] - (long long)offsets[p];
-    len = len < 0 ? 0 : (len > (long long)n_matches ? (long long)n_matches : len);
-    v = (int32_t)len;
-  }
-  counts[at] = v;
+  counts[at] = k == 0 ? list_length(offsets, p, n_matches) : 0;
 }
 
 // The sizes of the pair at P, or false when the pair must not be evaluated: W1, H1, W2, H2 not whole numbers in

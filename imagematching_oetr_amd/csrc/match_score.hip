@@ -1,18 +1,16 @@
 // Scoring matches against depth and pose (include/oetr_match_score.h): the reference's compute_epipolar_error,
 // get_episym and get_projected_kp + get_truesym for many match lists over a depth-map set, in one call.
 //
-// k_match_score: one thread per match row, 256-thread workgroups.  The row finds its list by binary search in the
-// offsets (largest p with offsets[p] <= m, scored only if m < offsets[p+1]), makes the vouching test of
-// k_covis_warp_indexed on its pair's two table rows (without max_pixels: the grid is over matches) and then runs
-// tests/match_score_oracle.py::score LITERALLY: float64, every operation rounded on its own in the order and with
+// k_match_score: one thread per match row, 256-thread workgroups.  The row finds its list (match_list.h), makes the
+// vouching test of k_covis_warp_indexed on its pair's two table rows (without max_pixels: the grid is over matches)
+// and then runs tests/match_score_oracle.py::score LITERALLY: float64, every operation rounded on its own in the order and with
 // the parentheses written there (no contraction into FMAs: rint() and the "<" tests are discontinuous and the
 // parity target is a float64 numpy program).  E = [t]x R, m = R^T t and px_thr * px_thr are computed per thread
-// with the same individual operations.  Twelve float64 divisions per row.  The search is made ONCE PER WAVE for the
-// wave's first row, with scalar loads; a wave whose rows all lie in that list - the common case - also takes its two
-// indices, two table rows and 20 parameters by scalar loads, so that a row's chain of dependent VECTOR loads is its
-// keypoints and its two depth pixels.  (A search and the pair's data per lane, 16 dependent vector loads, cost 6.4x
-// a copy of the call's bytes; profiles/match_score_probe.json has what this form costs.)  Lanes past the first
-// row's list search for themselves, and such a wave loads per lane.
+// with the same individual operations.  Twelve float64 divisions per row.  A wave whose rows all lie in the list of
+// its first row - the common case - takes its two indices, two table rows and 20 parameters by scalar loads, as it
+// took that list, so that a row's chain of dependent VECTOR loads is its keypoints and its two depth pixels.  (A
+// search and the pair's data per lane, 16 dependent vector loads, cost 6.4x a copy of the call's bytes;
+// profiles/match_score_probe.json has what this form costs.)  A wave that straddles lists loads per lane.
 // Nothing is dereferenced on the strength of device data alone: a row index is below the host's n_matches, a pair
 // number inside [0, n_pairs) by construction of the search, a map index tested against n_maps, a depth pixel
 // tested in float64 against its row's H, W before the conversion to an integer.
@@ -28,23 +26,13 @@
 #include "../../include/oetr_match_score.h"
 #include "common.h"
 #include "depth_pose.h"
+#include "match_list.h"
 
 namespace oetr {
 
 constexpr int MATCH_THREADS = 256;
 constexpr int MATCH_PARAMS = OETR_MATCH_SCORE_PARAM_DOUBLES;
 constexpr int MATCH_COUNTERS = OETR_MATCH_SCORE_COUNTERS;
-
-// The largest p in [0, n_pairs) with offsets[p] <= m, or -1: the number of such entries, less one (the offsets are
-// assumed non-decreasing).  Reads offsets[0 .. n_pairs-1] only.
-__device__ __forceinline__ int match_find_list(const int32_t* __restrict__ offsets, int n_pairs, int m) {
-  int lo = 0, hi = n_pairs;
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);     // lo <= mid < hi <= n_pairs
-    if (offsets[mid] <= m) lo = mid + 1; else hi = mid;
-  }
-  return lo - 1;
-}
 
 struct MatchRow {
   double epi, sym, r12, r21;
@@ -114,24 +102,8 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_match_score(
     u1 = k1[at], v1 = k1[at + 1], u2 = k2[at], v2 = k2[at + 1];
   }
 
-  // The list of the wave's FIRST row, searched once per wave with wave-uniform (scalar) loads; rows ascend with the
-  // lane, so for non-decreasing offsets a later row m < offsets[p0 + 1] belongs to p0 too: offsets[p0] <= row0 <= m
-  // and every later offset is > m.  Only a lane past that boundary searches for itself.
-  const int64_t row0 = (int64_t)blockIdx.x * MATCH_THREADS + (int64_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x);
-  int p0 = -1, end0 = 0;
-  if (row0 < (int64_t)n_matches) {
-    p0 = __builtin_amdgcn_readfirstlane(match_find_list(offsets, n_pairs, (int)row0));
-    if (p0 >= 0) end0 = offsets[p0 + 1];                            // p0 + 1 <= n_pairs
-  }
-  int p = -1;
-  if (active) {
-    if (p0 >= 0 && m < end0) {
-      p = p0;
-    } else {
-      p = match_find_list(offsets, n_pairs, m);
-      if (p >= 0 && !(m < offsets[p + 1])) p = -1;
-    }
-  }
+  int p0, p;                                                        // the wave's first row's list, this row's
+  wave_find_list<MATCH_THREADS>(offsets, n_pairs, n_matches, active, m, p0, p);
 
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   MatchRow r = {nan, nan, nan, nan, 0u};
@@ -166,15 +138,13 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_match_score(
   // counters 1..4 (counter 0, the list length, is k_match_finish's).  Every lane of the wave arrives here.
   const bool c_epi = (flag & OETR_MATCH_EPI) != 0, c_sym = (flag & OETR_MATCH_EPISYM) != 0;
   const bool c_both = (flag & 3u) == 3u, c_px = (flag & OETR_MATCH_REPROJ) != 0;
-  const unsigned long long counting = __ballot(counted >= 0);
-  if (counting == 0ull) return;                                     // wave-uniform
-  const int first = __shfl(counted, __ffsll((long long)counting) - 1, 64);
-  const bool one_pair = __ballot(counted >= 0 && counted != first) == 0ull;
-  if (one_pair) {
+  const WaveCounted w = wave_counted(counted);
+  if (!w.any) return;                                               // wave-uniform
+  if (w.one_pair) {
     const int n_epi = __popcll(__ballot(c_epi)), n_sym = __popcll(__ballot(c_sym));
     const int n_both = __popcll(__ballot(c_both)), n_px = __popcll(__ballot(c_px));
     if ((threadIdx.x & 63) == 0) {
-      int32_t* c = counts + (size_t)first * MATCH_COUNTERS;         // 0 <= first < n_pairs
+      int32_t* c = counts + (size_t)w.first * MATCH_COUNTERS;       // 0 <= first < n_pairs
       if (n_epi) atomicAdd(c + 1, n_epi);
       if (n_sym) atomicAdd(c + 2, n_sym);
       if (n_both) atomicAdd(c + 3, n_both);
@@ -210,9 +180,7 @@ __global__ void k_match_finish(const oetr_covis_map* __restrict__ maps, int n_ma
     for (int k = 0; k < MATCH_COUNTERS; ++k) c[k] = -1;
     return;
   }
-  long long len = (long long)offsets[p + 1] - (long long)offsets[p];
-  len = len < 0 ? 0 : (len > (long long)n_matches ? (long long)n_matches : len);
-  c[0] = (int32_t)len;
+  c[0] = list_length(offsets, p, n_matches);
   if (epi_thr != epi_thr) c[1] = -1;
   if (sym_thr != sym_thr) c[2] = -1;
   if (px_thr != px_thr) c[4] = -1;

@@ -26,22 +26,9 @@ import numpy as np
 import torch
 
 from . import hip_engine
-from ._inputs import _is_host, _keypoints, _offsets_of, _refuse_float64, _refuse_host_inputs_in_capture, _upload
+from ._inputs import (NO_CPU, _device_of, _host_names, _is_host, _match_keypoints, _match_list_args, _match_offsets,
+                      _ptr, _refuse_host_inputs_in_capture, _shape_of, _upload, _workspace)
 from .hip_engine import COVIS_MAX_SIDE, HOMOGRAPHY_MAX_THRESHOLDS, HOMOGRAPHY_PARAM_DOUBLES, _check, _stream
-
-NO_CPU = 'There is no CPU implementation.'
-
-
-def _device_of(what, tensors):
-    """The GPU of the first device tensor among ``tensors``, else the current GPU; raises without one."""
-    for t in tensors:
-        if torch.is_tensor(t) and t.is_cuda:
-            return t.device
-    if not torch.cuda.is_available():
-        raise RuntimeError(f'{what} needs a GPU (HIP) device: the inputs are on the CPU and no GPU is present. '
-                           + NO_CPU)
-    return torch.device('cuda', torch.cuda.current_device())
-
 
 def _f64(x, dev):
     """``x`` as a float64 tensor on ``dev``: a device tensor converted there, a host array uploaded (blocking)."""
@@ -107,7 +94,7 @@ def rescale_homography(H, scale1, scale2):
 def _blocks(params_or_H, dev, size1=None, size2=None):
     """float64 ``[P,16]`` blocks on ``dev`` of either form of the first argument."""
     x = params_or_H
-    shape = tuple(x.shape) if hasattr(x, 'shape') else tuple(np.asarray(x).shape)
+    shape = _shape_of(x)
     if len(shape) == 2 and shape[1] == HOMOGRAPHY_PARAM_DOUBLES:
         return _upload('params', x, torch.float64, shape, dev)
     return homography_params(x, size1, size2, device=dev)
@@ -135,36 +122,19 @@ def score_matches_homography(params_or_H, k1, k2, lengths=None, offsets=None, th
     when every input is a device tensor (a replay scores what the keypoint, offset and parameter
     tensors hold at replay time).  ``out``: the result of an earlier call of the same sizes, written
     into again with no allocation."""
-    if (lengths is None) == (offsets is None):
-        raise ValueError('give exactly one of `lengths` (host sequence) and `offsets` (device int32 [P+1])')
-    _refuse_float64('k1', k1)
-    _refuse_float64('k2', k2)
+    _match_list_args(k1, k2, lengths, offsets)
     thresholds = tuple(thresholds)
     T = len(thresholds)
     if T > HOMOGRAPHY_MAX_THRESHOLDS:
         raise ValueError(f'at most {HOMOGRAPHY_MAX_THRESHOLDS} thresholds, got {T}')
     dev = _device_of('score_matches_homography', (params_or_H, k1, k2, offsets))
-    host_inputs = [n for n, x in (('params_or_H', params_or_H), ('k1', k1), ('k2', k2), ('offsets', offsets))
-                   if x is not None and _is_host(x)]
-    if lengths is not None:
-        host_inputs.append('lengths')
+    host_inputs = _host_names((('params_or_H', params_or_H), ('k1', k1), ('k2', k2), ('offsets', offsets)), lengths)
     with torch.cuda.device(dev):
         _refuse_host_inputs_in_capture(host_inputs)
-        k1, k2 = _keypoints('k1', k1, dev, 'other inputs'), _keypoints('k2', k2, dev, 'other inputs')
-        M = int(k1.shape[0])
-        if int(k2.shape[0]) != M:
-            raise ValueError(f'k1 has {M} rows, k2 {int(k2.shape[0])}')
-        if M > 2 ** 31 - 1:
-            raise ValueError('more than 2^31 - 1 matches in one call')
+        k1, k2, M = _match_keypoints(k1, k2, dev, 'other inputs')
         params = _blocks(params_or_H, dev)
         P = int(params.shape[0])
-        if lengths is not None:
-            lengths = [int(n) for n in lengths]
-            if len(lengths) != P or any(n < 0 for n in lengths) or sum(lengths) != M:
-                raise ValueError(f'`lengths` must hold {P} non-negative lengths summing to {M} rows')
-            offsets = _offsets_of(lengths, dev)
-        else:
-            offsets = _upload('offsets', offsets, torch.int32, (P + 1,), dev)
+        offsets = _match_offsets(lengths, offsets, P, M, dev)
         if out is None:
             out = {'counts': torch.zeros(P, 1 + T, dtype=torch.int32, device=dev)}
             if values:
@@ -178,11 +148,10 @@ def score_matches_homography(params_or_H, k1, k2, lengths=None, offsets=None, th
                 out['dist_sq'].fill_(math.nan)
             return out
         lib = hip_engine.load_library()
-        ptr = lambda t: t.data_ptr() if t.numel() else None
         thr = (ctypes.c_double * max(T, 1))(*(float(t) for t in thresholds))
         _check(lib, lib.oetr_homography_match_score(
-            params.data_ptr(), offsets.data_ptr(), P, ptr(k1), ptr(k2), M, thr, T,
-            ptr(out['dist_sq']) if values else None, out['counts'].data_ptr(), _stream(dev)),
+            params.data_ptr(), offsets.data_ptr(), P, _ptr(k1), _ptr(k2), M, thr, T,
+            _ptr(out['dist_sq']) if values else None, out['counts'].data_ptr(), _stream(dev)),
             'oetr_homography_match_score')
         # what the enqueued kernels read stays referenced as long as the result does
         out['_inputs'] = (params, offsets, k1, k2)
@@ -271,10 +240,7 @@ def overlap_boxes_from_homography(params_or_H, size1=None, size2=None, out=None,
         clamp = lambda v: int(min(max(math.ceil(v) if math.isfinite(v) else 1, 1), COVIS_MAX_SIDE))
         max_h1, max_w1 = clamp(float(max_size1[0])), clamp(float(max_size1[1]))
         lib = hip_engine.load_library()
-        need = int(lib.oetr_homography_workspace_bytes(n))
-        workspace = out.get('workspace')
-        if workspace is None or workspace.numel() < need:
-            workspace = out['workspace'] = torch.empty(need, dtype=torch.uint8, device=dev)
+        workspace = _workspace(out, int(lib.oetr_homography_workspace_bytes(n)), dev)
         _check(lib, lib.oetr_homography_boxes(
             params.data_ptr(), n, max_h1, max_w1, workspace.data_ptr(), workspace.numel(),
             out['overlap_box1'].data_ptr(), out['overlap_box2'].data_ptr(), out['overlap_valid'].data_ptr(),

@@ -26,8 +26,8 @@ import numpy as np
 import torch
 
 from . import hip_engine
-from ._inputs import (_is_host, _keypoints, _offsets_of, _pair_blocks, _pair_tensor, _refuse_float64,
-                      _refuse_host_inputs_in_capture, _upload)
+from ._inputs import (_host_names, _is_host, _keypoints, _offsets_of, _pair_blocks, _pair_tensor, _ptr,
+                      _refuse_float64, _refuse_host_inputs_in_capture, _upload)
 from .hip_engine import KEYPOINT_SCORE_HEAD_COUNTERS, KEYPOINT_SCORE_MAX_THRESHOLDS, _check, _stream
 from .match_score import match_params
 
@@ -84,7 +84,7 @@ def score_keypoints(depth_set, pair_index, keypoints, thresholds=(1, 2, 3, 5), n
         raise RuntimeError(f'score_keypoints needs a depth-map set on a GPU (HIP) device, got {dev}. There is no CPU '
                            'implementation.')
     n_maps = len(depth_set)
-    host_inputs = [n for n, x in (('pair_index', pair_index), ('params', params)) if x is not None and _is_host(x)]
+    host_inputs = _host_names((('pair_index', pair_index), ('params', params)))
     if concatenated:
         host_inputs += [n for n, x in (('keypoints[0]', keypoints[0]), ('keypoints[1]', keypoints[1])) if _is_host(x)]
     else:
@@ -133,12 +133,11 @@ def score_keypoints(depth_set, pair_index, keypoints, thresholds=(1, 2, 3, 5), n
             return out
         idx1, idx2, table, params = _pair_blocks(depth_set, pair_index, params, match_params)
         lib = hip_engine.load_library()
-        ptr = lambda t: t.data_ptr() if t.numel() else None
         thr = (ctypes.c_double * max(T, 1))(*thresholds)
         _check(lib, lib.oetr_keypoint_repeatability(
-            table.data_ptr(), n_maps, ptr(cat), N, kp_offsets.data_ptr(), idx1.data_ptr(), idx2.data_ptr(),
+            table.data_ptr(), n_maps, _ptr(cat), N, kp_offsets.data_ptr(), idx1.data_ptr(), idx2.data_ptr(),
             params.data_ptr(), P, thr if T else None, T, max_kp, out['counts'].data_ptr(),
-            ptr(out['nearest']) if nearest else None, ptr(out['dist_sq']) if nearest else None, _stream(dev)),
+            _ptr(out['nearest']) if nearest else None, _ptr(out['dist_sq']) if nearest else None, _stream(dev)),
             'oetr_keypoint_repeatability')
         # what the enqueued kernels read stays referenced as long as the result does
         out['_inputs'] = (table, idx1, idx2, params, kp_offsets, cat)

@@ -21,8 +21,8 @@ import numpy as np
 import torch
 
 from . import hip_engine
-from ._inputs import (_is_host, _keypoints, _offsets_of, _refuse_float64, _refuse_host_inputs_in_capture,
-                      _upload)
+from ._inputs import (_host_names, _is_host, _keypoints, _offsets_of, _ptr, _refuse_float64,
+                      _refuse_host_inputs_in_capture, _upload)
 from .crop_batch import OverlapCropBatch
 from .hip_engine import MATCH_ASSEMBLY_COUNTERS, _check, _CropInfo, _stream
 
@@ -98,7 +98,7 @@ def assemble_matches(crops, scales, kp0, kp1, matches, conf=None, offsets0=None,
     named = [('scales', scales), ('offsets0', offsets0), ('offsets1', offsets1)]
     if joined:
         named += [('kp0', kp0), ('kp1', kp1), ('matches', matches), ('conf', conf)]
-    host_inputs = [n for n, x in named if x is not None and _is_host(x)]
+    host_inputs = _host_names(named)
     if not joined:
         host_inputs.append('per-pair lengths')
         host_inputs += [n for n, seq in (('kp0', kp0), ('kp1', kp1), ('matches', matches), ('conf', conf))
@@ -168,12 +168,11 @@ def assemble_matches(crops, scales, kp0, kp1, matches, conf=None, offsets0=None,
             if out[name].data_ptr() % align:
                 raise ValueError(f"`out['{name}']` must start on a multiple of {align} bytes (the kernel writes whole "
                                  'rows as vectors); hand back the tensors an earlier call allocated')
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
         _check(lib, lib.oetr_assemble_matches(
-            info.data_ptr(), scales.data_ptr(), P, ptr(kp0), offsets0.data_ptr(), N0, ptr(kp1), offsets1.data_ptr(), N1,
-            ptr(matches), matches.element_size(), ptr(conf), int(min_matches) if select else 0,
-            out['_workspace'].data_ptr(), ws_bytes, ptr(out['origin0']), ptr(out['origin1']), ptr(out['index0']),
-            ptr(out['index1']), ptr(out['k1']), ptr(out['k2']), ptr(out.get('mconf')), out['offsets'].data_ptr(),
+            info.data_ptr(), scales.data_ptr(), P, _ptr(kp0), offsets0.data_ptr(), N0, _ptr(kp1), offsets1.data_ptr(),
+            N1, _ptr(matches), matches.element_size(), _ptr(conf), int(min_matches) if select else 0,
+            out['_workspace'].data_ptr(), ws_bytes, _ptr(out['origin0']), _ptr(out['origin1']), _ptr(out['index0']),
+            _ptr(out['index1']), _ptr(out['k1']), _ptr(out['k2']), _ptr(out.get('mconf')), out['offsets'].data_ptr(),
             out['counts'].data_ptr(), out['few'].data_ptr() if select else None,
             out['n_few'].data_ptr() if select else None, _stream(dev)), 'oetr_assemble_matches')
         # what the enqueued kernels read stays referenced as long as the result does

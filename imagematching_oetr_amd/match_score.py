@@ -19,8 +19,8 @@ import math
 import torch
 
 from . import hip_engine
-from ._inputs import (_is_host, _keypoints, _offsets_of, _pair_blocks, _pair_tensor, _refuse_float64,
-                      _refuse_host_inputs_in_capture, _upload)
+from ._inputs import (_host_names, _match_keypoints, _match_list_args, _match_offsets, _pair_blocks, _pair_tensor,
+                      _ptr, _refuse_host_inputs_in_capture)
 from .covis_set import pair_params
 from .hip_engine import MATCH_SCORE_COUNTERS, _check, _stream
 
@@ -67,35 +67,19 @@ def score_matches(depth_set, pair_index, k1, k2, lengths=None, offsets=None, par
     offset, index and parameter tensors hold at replay time); use the set once before the capture, so
     that its table is uploaded outside it.  ``out``: the result of an earlier call
     of the same sizes, written into again with no allocation."""
-    if (lengths is None) == (offsets is None):
-        raise ValueError('give exactly one of `lengths` (host sequence) and `offsets` (device int32 [P+1])')
-    _refuse_float64('k1', k1)
-    _refuse_float64('k2', k2)
+    _match_list_args(k1, k2, lengths, offsets)
     dev = torch.device(depth_set.device)
     if dev.type != 'cuda':
         raise RuntimeError(f'score_matches needs a depth-map set on a GPU (HIP) device, got {dev}. There is no CPU '
                            'implementation.')
-    host_inputs = [n for n, x in (('pair_index', pair_index), ('k1', k1), ('k2', k2), ('offsets', offsets),
-                                  ('params', params)) if x is not None and _is_host(x)]
-    if lengths is not None:
-        host_inputs.append('lengths')
+    host_inputs = _host_names((('pair_index', pair_index), ('k1', k1), ('k2', k2), ('offsets', offsets),
+                               ('params', params)), lengths)
     with torch.cuda.device(dev):
         _refuse_host_inputs_in_capture(host_inputs)
-        k1, k2 = _keypoints('k1', k1, dev, 'depth-map set'), _keypoints('k2', k2, dev, 'depth-map set')
-        M = int(k1.shape[0])
-        if int(k2.shape[0]) != M:
-            raise ValueError(f'k1 has {M} rows, k2 {int(k2.shape[0])}')
-        if M > 2 ** 31 - 1:
-            raise ValueError('more than 2^31 - 1 matches in one call')
+        k1, k2, M = _match_keypoints(k1, k2, dev, 'depth-map set')
         pair_index = _pair_tensor(dev, pair_index)
         P = int(pair_index.shape[0])
-        if lengths is not None:
-            lengths = [int(n) for n in lengths]
-            if len(lengths) != P or any(n < 0 for n in lengths) or sum(lengths) != M:
-                raise ValueError(f'`lengths` must hold {P} non-negative lengths summing to {M} rows')
-            offsets = _offsets_of(lengths, dev)
-        else:
-            offsets = _upload('offsets', offsets, torch.int32, (P + 1,), dev)
+        offsets = _match_offsets(lengths, offsets, P, M, dev)
         if out is None:
             out = {'flags': torch.zeros(M, dtype=torch.uint8, device=dev),
                    'counts': torch.zeros(P, MATCH_SCORE_COUNTERS, dtype=torch.int32, device=dev)}
@@ -113,10 +97,9 @@ def score_matches(depth_set, pair_index, k1, k2, lengths=None, offsets=None, par
         idx1, idx2, table, params = _pair_blocks(depth_set, pair_index, params, match_params)
         thr = [math.nan if t is None else float(t) for t in (epi_thr, sym_thr, px_thr)]
         lib = hip_engine.load_library()
-        ptr = lambda t: t.data_ptr() if t.numel() else None
         _check(lib, lib.oetr_match_score(
             table.data_ptr(), len(depth_set), idx1.data_ptr(), idx2.data_ptr(), params.data_ptr(), offsets.data_ptr(), P,
-            ptr(k1), ptr(k2), M, thr[0], thr[1], thr[2], ptr(out['values']) if values else None, ptr(out['flags']),
+            _ptr(k1), _ptr(k2), M, thr[0], thr[1], thr[2], _ptr(out['values']) if values else None, _ptr(out['flags']),
             out['counts'].data_ptr(), _stream(dev)), 'oetr_match_score')
         # what the enqueued kernels read stays referenced as long as the result does
         out['_inputs'] = (table, idx1, idx2, params, offsets, k1, k2)

@@ -16,17 +16,13 @@ tensor.
 """
 import math
 
-import numpy as np
 import torch
 
 from . import hip_engine
-from ._inputs import _is_host, _keypoints, _offsets_of, _refuse_float64, _refuse_host_inputs_in_capture, _upload
-from .homography import _device_of
+from ._inputs import (_device_of, _host_names, _match_keypoints, _match_list_args, _match_offsets, _ptr,
+                      _refuse_host_inputs_in_capture, _shape_of, _upload, _workspace)
 from .hip_engine import (MATCH_SCORE_PARAM_DOUBLES, POSE_RANSAC_COUNTERS, POSE_RANSAC_MAX_HYPOTHESES,
                          POSE_RANSAC_MAX_MODELS, _check, _stream)
-
-def _shape_of(x):
-    return tuple(x.shape) if hasattr(x, 'shape') else tuple(np.asarray(x).shape)
 
 
 @torch.no_grad()
@@ -57,10 +53,7 @@ def estimate_poses(params, k1, k2, lengths=None, offsets=None, n_hyp=256, px_thr
     Enqueues on torch's current stream and reads nothing back, so it can be captured into a HIP graph when
     every input is a device tensor.  ``out``: the result of an earlier call of the same sizes, written into
     again with no allocation."""
-    if (lengths is None) == (offsets is None):
-        raise ValueError('give exactly one of `lengths` (host sequence) and `offsets` (device int32 [P+1])')
-    _refuse_float64('k1', k1)
-    _refuse_float64('k2', k2)
+    _match_list_args(k1, k2, lengths, offsets)
     if models is None and not 1 <= int(n_hyp) <= POSE_RANSAC_MAX_HYPOTHESES:
         raise ValueError(f'n_hyp must be in 1..{POSE_RANSAC_MAX_HYPOTHESES}, got {n_hyp}')
     if not (math.isfinite(float(px_thr)) and float(px_thr) > 0):
@@ -70,30 +63,17 @@ def estimate_poses(params, k1, k2, lengths=None, offsets=None, n_hyp=256, px_thr
         if len(shape) != 3 or shape[2] != 9 or not 1 <= shape[1] <= POSE_RANSAC_MAX_MODELS:
             raise ValueError(f'models must be [P,n,9] with n in 1..{POSE_RANSAC_MAX_MODELS}, got {shape}')
     dev = _device_of('estimate_poses', (params, k1, k2, offsets, pair_ids, models))
-    host_inputs = [n for n, x in (('params', params), ('k1', k1), ('k2', k2), ('offsets', offsets),
-                                  ('pair_ids', pair_ids), ('models', models)) if x is not None and _is_host(x)]
-    if lengths is not None:
-        host_inputs.append('lengths')
+    host_inputs = _host_names((('params', params), ('k1', k1), ('k2', k2), ('offsets', offsets),
+                               ('pair_ids', pair_ids), ('models', models)), lengths)
     with torch.cuda.device(dev):
         _refuse_host_inputs_in_capture(host_inputs)
-        k1, k2 = _keypoints('k1', k1, dev, 'other inputs'), _keypoints('k2', k2, dev, 'other inputs')
-        M = int(k1.shape[0])
-        if int(k2.shape[0]) != M:
-            raise ValueError(f'k1 has {M} rows, k2 {int(k2.shape[0])}')
-        if M > 2 ** 31 - 1:
-            raise ValueError('more than 2^31 - 1 matches in one call')
+        k1, k2, M = _match_keypoints(k1, k2, dev, 'other inputs')
         pshape = _shape_of(params)
         if len(pshape) != 2 or pshape[1] != MATCH_SCORE_PARAM_DOUBLES:
             raise ValueError(f'params must be [P,{MATCH_SCORE_PARAM_DOUBLES}], got {pshape}')
         P = int(pshape[0])
         params = _upload('params', params, torch.float64, (P, MATCH_SCORE_PARAM_DOUBLES), dev)
-        if lengths is not None:
-            lengths = [int(n) for n in lengths]
-            if len(lengths) != P or any(n < 0 for n in lengths) or sum(lengths) != M:
-                raise ValueError(f'`lengths` must hold {P} non-negative lengths summing to {M} rows')
-            offsets = _offsets_of(lengths, dev)
-        else:
-            offsets = _upload('offsets', offsets, torch.int32, (P + 1,), dev)
+        offsets = _match_offsets(lengths, offsets, P, M, dev)
         if pair_ids is not None:
             pair_ids = _upload('pair_ids', pair_ids, torch.int32, (P,), dev)
         if models is not None:
@@ -116,17 +96,13 @@ def estimate_poses(params, k1, k2, lengths=None, offsets=None, n_hyp=256, px_thr
                 out['inliers'].zero_()
             return out
         lib = hip_engine.load_library()
-        need = int(lib.oetr_pose_ransac_workspace_bytes(P, n_models))
-        workspace = out.get('workspace')
-        if workspace is None or workspace.numel() < need:
-            workspace = out['workspace'] = torch.empty(need, dtype=torch.uint8, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        workspace = _workspace(out, int(lib.oetr_pose_ransac_workspace_bytes(P, n_models)), dev)
         _check(lib, lib.oetr_pose_ransac(
-            params.data_ptr(), offsets.data_ptr(), ptr(pair_ids), P, ptr(k1), ptr(k2), M,
-            int(n_hyp) if models is None else 0, int(seed) & 0xFFFFFFFF, float(px_thr), ptr(models),
+            params.data_ptr(), offsets.data_ptr(), _ptr(pair_ids), P, _ptr(k1), _ptr(k2), M,
+            int(n_hyp) if models is None else 0, int(seed) & 0xFFFFFFFF, float(px_thr), _ptr(models),
             n_models if models is not None else 0, workspace.data_ptr(), workspace.numel(), out['model'].data_ptr(),
             out['pose'].data_ptr(), out['cosines'].data_ptr(), out['counts'].data_ptr(),
-            ptr(out['inliers']) if inliers else None, _stream(dev)), 'oetr_pose_ransac')
+            _ptr(out['inliers']) if inliers else None, _stream(dev)), 'oetr_pose_ransac')
         # what the enqueued kernels read stays referenced as long as the result does
         out['_inputs'] = (params, offsets, k1, k2, pair_ids, models)
     return out
