@@ -1102,7 +1102,7 @@ int set_last_error(int status, const char* msg);
 oetr_status entry_fail(const char* entry, oetr_status status, const std::string& msg);
 // ... and the outcome of a HIP call or launch `what` made by it: OETR_OK, or OETR_ERR_HIP "<entry>: <what>: <HIP's text>"
 oetr_status entry_hip(const char* entry, hipError_t e, const char* what);
-// p[0 .. n) = 0 on stream s, by the library's one clearing kernel k_clear_i32 (match_score.hip, which says why a kernel);
+// p[0 .. n) = 0 on stream s, by the library's int32 clearing kernel k_clear_i32 (match_score.hip, which says why a kernel);
 // 0 <= n <= INT32_MAX.  Returns the launch's hipGetLastError().
 hipError_t clear_i32(int32_t* p, int64_t n, hipStream_t s);
 // Repacked weights of one encoder layer (device pointers).

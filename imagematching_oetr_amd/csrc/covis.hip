@@ -7,8 +7,8 @@
 // float64 with every operation rounded on its own, in the reference's order (no contraction into FMAs: trunc() and
 // "< 0.5" are discontinuous, and the parity target is a float64 numpy program).  The pair's 37 parameters are
 // wave-uniform loads.  Per thread: eight box bounds and a count in registers, all kept as MAXIMA of non-negative codes
-// (a minimum m is kept as SIDE - m, a maximum M as M + 1; 0 = nothing seen), so that the all-zero accumulator a memset
-// leaves is the neutral element.  Wave reduction by __shfl_xor over 64 lanes, one LDS step per workgroup, then one set
+// (a minimum m is kept as SIDE - m, a maximum M as M + 1; 0 = nothing seen), so that the all-zero accumulator the
+// call's clear leaves (clear_acc: a kernel, not a memset node) is the neutral element.  Wave reduction by __shfl_xor over 64 lanes, one LDS step per workgroup, then one set
 // of integer atomicMax / atomicAdd per workgroup that saw an inlier: integer atomics commute, the result does not
 // depend on arrival order.  k_covis_finish (one thread per pair) decodes the accumulators into float32 boxes, the
 // valid byte and the count.  Masks are plain byte stores of 1 into memory the call cleared.
@@ -263,9 +263,51 @@ __global__ __launch_bounds__(SELECT_THREADS) void k_covis_select(const float* __
   if (threadIdx.x == 0) *n_kept = written;
 }
 
+constexpr int CLEAR_THREADS = 256;
+constexpr unsigned CLEAR_MAX_BLOCKS = 4096;                       // past that a thread stores more than once
+
+// a[0 .. n) = 0 and b[0 .. n) = 0 (grid y: 0 = a, 1 = b): the byte-sized sibling of k_clear_i32 for the two masks,
+// a kernel for the same reason (see clear_i32 in match_score.hip).  16-byte stores over each array's aligned body,
+// grid-stride; byte stores on the at most 15 bytes before and the at most 15 bytes after it.
+__global__ __launch_bounds__(CLEAR_THREADS) void k_clear_u8_pair(uint8_t* __restrict__ a, uint8_t* __restrict__ b,
+                                                                 size_t n) {
+  uint8_t* __restrict__ p = blockIdx.y == 0 ? a : b;
+  const size_t to_aligned = (size_t)((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u);
+  const size_t head = to_aligned < n ? to_aligned : n;            // bytes before the first 16-byte boundary
+  const size_t body = (n - head) / 16;                            // whole 16-byte words: head + 16 * body <= n
+  const size_t tail = head + 16 * body;                           // n - tail <= 15
+  uint4* __restrict__ q = reinterpret_cast<uint4*>(p + head);
+  const size_t tid = (size_t)blockIdx.x * CLEAR_THREADS + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * CLEAR_THREADS;
+  for (size_t i = tid; i < body; i += stride) q[i] = make_uint4(0u, 0u, 0u, 0u);
+  if (tid < head) p[tid] = 0;                                     // the grid has at least CLEAR_THREADS threads
+  if (tid < n - tail) p[tail + tid] = 0;
+}
+
 namespace {
 
 constexpr int COVIS_MAX_GRID_Y = 65535;                           // the grid's y extent: more pairs, more launches
+
+// The accumulators of n_pairs pairs zeroed by the library's clearing kernel, not by a memset node: captured into a
+// graph, hipMemsetAsync(acc, 0, 192) left a foreign 16-byte pattern in the accumulators on the graph's second replay
+// after device copies between the replays (tests/test_gpu_covis.py: the ragged-clears test; the fault clear_i32 in
+// match_score.hip records).  One launch up to INT32_MAX / COVIS_ACC pairs, clear_i32's int count.
+hipError_t clear_acc(int* acc, int n_pairs, hipStream_t s) {
+  constexpr int64_t chunk = INT32_MAX / COVIS_ACC;
+  for (int64_t p0 = 0; p0 < (int64_t)n_pairs; p0 += chunk) {
+    const int64_t n = (int64_t)n_pairs - p0 < chunk ? (int64_t)n_pairs - p0 : chunk;
+    if (hipError_t e = clear_i32(acc + p0 * COVIS_ACC, n * COVIS_ACC, s)) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t clear_masks(uint8_t* mask1, uint8_t* mask2, size_t n, hipStream_t s) {
+  const size_t words = n / 16 + 1;
+  const size_t want = (words + CLEAR_THREADS - 1) / CLEAR_THREADS;
+  const unsigned blocks = (unsigned)(want < CLEAR_MAX_BLOCKS ? want : CLEAR_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_clear_u8_pair, dim3(blocks, 2), dim3(CLEAR_THREADS), 0, s, mask1, mask2, n);
+  return hipGetLastError();
+}
 
 }  // namespace
 }  // namespace oetr
@@ -298,10 +340,9 @@ oetr_status oetr_covis_boxes(const float* depth1, const float* depth2, const dou
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n_pix = (size_t)H * W;
   int* acc = static_cast<int*>(workspace);
-  if (oetr_status rc = entry_hip(me, hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)")) return rc;
+  if (oetr_status rc = entry_hip(me, clear_acc(acc, n_pairs, s), "k_clear_i32")) return rc;
   if (mask1) {
-    if (oetr_status rc = entry_hip(me, hipMemsetAsync(mask1, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask1)")) return rc;
-    if (oetr_status rc = entry_hip(me, hipMemsetAsync(mask2, 0, n_pix * n_pairs, s), "hipMemsetAsync(mask2)")) return rc;
+    if (oetr_status rc = entry_hip(me, clear_masks(mask1, mask2, n_pix * n_pairs, s), "k_clear_u8_pair")) return rc;
   }
   constexpr int max_pairs = COVIS_MAX_GRID_Y;
   const unsigned blocks = (unsigned)((n_pix + COVIS_PIX - 1) / COVIS_PIX);
@@ -338,7 +379,7 @@ oetr_status oetr_covis_boxes_indexed(const oetr_covis_map* maps, int n_maps, con
                                             std::to_string(need));
   hipStream_t s = static_cast<hipStream_t>(stream);
   int* acc = static_cast<int*>(workspace);
-  if (oetr_status rc = entry_hip(me, hipMemsetAsync(acc, 0, need, s), "hipMemsetAsync(workspace)")) return rc;
+  if (oetr_status rc = entry_hip(me, clear_acc(acc, n_pairs, s), "k_clear_i32")) return rc;
   const int max_pix = (int)max_pixels;
   const unsigned blocks = (unsigned)((max_pix + COVIS_PIX - 1) / COVIS_PIX);
   for (int p0 = 0; p0 < n_pairs; p0 += COVIS_MAX_GRID_Y) {

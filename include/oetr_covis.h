@@ -61,8 +61,8 @@ size_t oetr_covis_workspace_bytes(int n_pairs);
  *     box2[p]         (min i, min j, max i, max j) over the inliers, float32; zeros when not valid
  *     mask1[p][v][u] = 1, mask2[p][j][i] = 1 for every inlier (uint8 [H][W], cleared by the call);
  *                     both NULL (no masks) or both set.
- * All pointers are device memory owned by the caller.  The call only enqueues on `stream` (two
- * kernels and the clearing memsets), reads nothing back and can be captured into a HIP graph; the
+ * All pointers are device memory owned by the caller.  The call only enqueues on `stream` (kernels
+ * alone: the clears are kernels too, no memset node), reads nothing back and can be captured into a HIP graph; the
  * reductions are integer atomics, so the results are bit-identical from run to run.
  *
  * Checked on the host before anything is enqueued: NULL depth / params / workspace / box / valid

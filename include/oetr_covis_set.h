@@ -54,7 +54,7 @@ size_t oetr_covis_set_workspace_bytes(int n_pairs);
  * index is outside [0, n_maps), the map's pointer is NULL, its H or W is outside 1..OETR_COVIS_MAX_SIDE, or its
  * H * W exceeds max_pixels.  The other pairs of the call are unaffected.
  *
- * The call only enqueues on `stream` (a clearing memset and two kernels, one more kernel per 65535 pairs),
+ * The call only enqueues on `stream` (a clearing kernel and two more, one more kernel per 65535 pairs; no memset node),
  * reads nothing back, allocates nothing and can be captured into a HIP graph; a replay sees the table, the
  * indices and the parameters the buffers hold at replay time.  The reductions are integer atomics, so the
  * results are bit-identical from run to run and do not depend on the order of the list.

@@ -181,6 +181,90 @@ def test_captured_into_a_hip_graph_and_replayed_on_new_inputs(gpu):
     assert_equals(eager, exp_a)
 
 
+GUARD = 64
+
+
+def _guarded(nbytes, gpu, skew=0):
+    """``nbytes`` of device memory between two guard regions, starting ``skew`` bytes past a 64-byte boundary ->
+    (the two guards, filled with 0xA5, and the slice between them)."""
+    whole = torch.full((GUARD + skew + nbytes + GUARD,), 0xA5, dtype=torch.uint8, device=gpu)
+    assert whole.data_ptr() % 64 == 0
+    return (whole[:GUARD + skew], whole[GUARD + skew + nbytes:]), whole[GUARD + skew:GUARD + skew + nbytes]
+
+
+def _guards_intact(guards):
+    return all(bool((g == 0xA5).all()) for g in guards)
+
+
+@pytest.mark.parametrize('n,h,w', [(3, 7, 9), (5, 5, 7)], ids=['189_bytes', '175_bytes'])
+def test_ragged_clears_replayed_three_times_with_copies_between(gpu, n, h, w):
+    """The call's clears under graph replay: the workspace (64 bytes a pair) and, with masks, two of ``n * h * w``
+    bytes - here 189 and 175, no multiple of 16.  While the clears were ``hipMemsetAsync`` nodes, the 3-pair capture
+    came back with a foreign pattern in its accumulators on the graph's SECOND replay after device copies, the
+    fault ``clear_i32`` (``csrc/match_score.hip``) records; they are kernels now (``clear_acc``, ``k_clear_u8_pair``).
+    Three replays with ``copy_`` of new scenes between them: after each, boxes, counts, valid and masks are the
+    restatement of what the inputs held, and the bytes around the masks and the workspace are untouched.  The second
+    set of scenes has no inlier at all where the first had many: nothing may be left."""
+    from imagematching_oetr_amd import hip_engine
+    from imagematching_oetr_amd.covis import covis_boxes
+    kinds = (('plane', 'trunc', 'plane', 'trunc', 'plane'), ('no_overlap', 'behind', 'no_overlap', 'behind', 'no_overlap'),
+             ('trunc', 'no_overlap', 'plane', 'plane', 'behind'))
+    rounds = [cvo.scene_batch(k[:n], h, w, seed=900 + 50 * r) for r, k in enumerate(kinds)]
+    assert sum(e['count'] for e in rounds[0][1]) > 0 and not any(e['valid'] for e in rounds[1][1])
+    assert (n * h * w) % 16 != 0
+    d1, d2, params = _device_inputs(rounds[0][0], gpu)
+    covis_boxes(d1, d2, params, masks=True)                       # loads the library's code objects
+    need = int(hip_engine.load_library().oetr_covis_workspace_bytes(n))
+    assert need == 64 * n
+    whole1, m1 = _guarded(n * h * w, gpu)
+    whole2, m2 = _guarded(n * h * w, gpu, skew=5)                  # mask 2 starts 5 bytes past a 16-byte boundary
+    whole_ws, ws = _guarded(need, gpu)
+    out = {'overlap_box1': torch.empty(n, 4, device=gpu), 'overlap_box2': torch.empty(n, 4, device=gpu),
+           'overlap_valid': torch.empty(n, dtype=torch.bool, device=gpu),
+           'overlap_count': torch.empty(n, dtype=torch.int32, device=gpu),
+           'overlap_mask1': m1.view(n, h, w), 'overlap_mask2': m2.view(n, h, w), 'workspace': ws}
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        assert covis_boxes(d1, d2, params, masks=True, out=out) is out
+    assert out['workspace'] is ws and out['overlap_mask1'].data_ptr() == m1.data_ptr()
+    for r, (arrays, expected) in enumerate(rounds):
+        if r:
+            new = _device_inputs(arrays, gpu)
+            d1.copy_(new[0]); d2.copy_(new[1]); params.copy_(new[2])
+        graph.replay()
+        torch.cuda.synchronize()
+        assert_equals({k: v for k, v in out.items() if k != 'workspace'}, expected)
+        assert _guards_intact(whole1) and _guards_intact(whole2) and _guards_intact(whole_ws), r
+
+
+def test_masks_larger_than_one_pass_of_the_clearing_kernel(gpu):
+    """``k_clear_u8_pair`` has at most ``CLEAR_MAX_BLOCKS`` blocks of ``CLEAR_THREADS`` threads a mask, 16 bytes a
+    thread and pass (both read from the source): 17 pairs of 1024 x 1024 are 17 MiB a mask, so the first threads
+    store a second time.  Masks full of 0xA5 beforehand; every byte is compared."""
+    import re
+    import imagematching_oetr_amd as pkg
+    from imagematching_oetr_amd.covis import covis_boxes
+    src = (Path(pkg.__file__).parent / 'csrc' / 'covis.hip').read_text()
+    threads = int(re.search(r'constexpr int CLEAR_THREADS = (\d+);', src).group(1))
+    blocks = int(re.search(r'constexpr unsigned CLEAR_MAX_BLOCKS = (\d+);', src).group(1))
+    n, side = 17, 1024
+    assert n * side * side > blocks * threads * 16
+    scenes = [cvo.checked_scene(kind, side, side, 40 + k) for k, kind in enumerate(('plane', 'no_overlap'))]
+    pick = [p % 2 for p in range(n)]
+    tile = lambda key: torch.from_numpy(np.stack([scenes[k][0][key] for k in (0, 1)])).to(gpu)[pick].contiguous()
+    params = torch.from_numpy(np.stack([cvo.param_block(scenes[k][0]) for k in pick])).to(gpu)
+    d1, d2 = tile('depth1'), tile('depth2')
+    out = covis_boxes(d1, d2, params, masks=True)
+    for key in ('overlap_mask1', 'overlap_mask2'):
+        out[key].fill_(0xA5)
+    covis_boxes(d1, d2, params, masks=True, out=out)
+    want1 = torch.from_numpy(np.stack([scenes[k][1]['mask1'] for k in (0, 1)])).to(gpu)[pick]
+    want2 = torch.from_numpy(np.stack([scenes[k][1]['mask2'] for k in (0, 1)])).to(gpu)[pick]
+    assert torch.equal(out['overlap_mask1'], want1) and torch.equal(out['overlap_mask2'], want2)
+    assert out['overlap_count'].tolist() == [scenes[k][1]['count'] for k in pick] and scenes[0][1]['count'] > 50000
+
+
 def test_on_a_side_stream(gpu):
     import imagematching_oetr_amd as pkg
     arrays, expected = cvo.scene_batch(('plane', 'trunc'), 192, 192, seed=700)

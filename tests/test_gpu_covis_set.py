@@ -236,6 +236,47 @@ def test_captured_into_a_hip_graph_and_replayed_on_new_indices(gpu):
         assert_pair(got, p, results[pair], pair)
 
 
+@pytest.mark.parametrize('n', [3, 14])
+def test_workspace_clear_replayed_three_times_with_copies_between(gpu, n):
+    """The call's workspace clear under graph replay (64 bytes a pair: 192 and 896 bytes; ``clear_acc``, a kernel
+    since a memset node of the stacked entry failed this pattern: ``tests/test_gpu_covis.py``).  Three replays with ``copy_`` of new indices between them: after each the boxes are the restatement of the pairs the
+    index tensor held, and the bytes around the workspace are untouched.  The second list's pairs look at view
+    ``AWAY_VIEW`` (no inlier) where the first list's have hundreds: nothing may be left in the accumulators."""
+    import imagematching_oetr_amd as pkg
+    from imagematching_oetr_amd import hip_engine
+    guard = 64
+    views, results = the_set()
+    ds = depth_set(gpu, views)
+    pairs = sorted(results)
+    seen = [p for p in pairs if results[p]['valid']]
+    away = [p for p in pairs if cso.AWAY_VIEW in p]
+    assert len(seen) >= 2 * n and len(away) >= n and not any(results[p]['valid'] for p in away)
+    rounds = [seen[:n], away[:n], seen[n:2 * n]]
+    index = torch.tensor(rounds[0], dtype=torch.int32, device=gpu)
+    pkg.overlap_boxes_indexed(ds, index)                             # uploads the table, loads the code objects
+    need = int(hip_engine.load_library().oetr_covis_set_workspace_bytes(n))
+    assert need == 64 * n
+    whole = torch.full((guard + need + guard,), 0xA5, dtype=torch.uint8, device=gpu)
+    ws = whole[guard:guard + need]
+    out = {'overlap_box1': torch.zeros(n, 4, device=gpu), 'overlap_box2': torch.zeros(n, 4, device=gpu),
+           'overlap_valid': torch.zeros(n, dtype=torch.bool, device=gpu),
+           'overlap_count': torch.zeros(n, dtype=torch.int32, device=gpu), 'workspace': ws}
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        assert pkg.overlap_boxes_indexed(ds, index, out=out) is out
+    assert out['workspace'] is ws
+    for r, listed in enumerate(rounds):
+        if r:
+            index.copy_(torch.tensor(listed, dtype=torch.int32))
+        graph.replay()
+        torch.cuda.synchronize()
+        got = host(out)
+        for p, pair in enumerate(listed):
+            assert_pair(got, p, results[pair], (r, pair))
+        assert bool((whole[:guard] == 0xA5).all()) and bool((whole[-guard:] == 0xA5).all()), r
+
+
 def test_on_a_side_stream(gpu):
     import imagematching_oetr_amd as pkg
     views, results = the_set()

@@ -1,7 +1,7 @@
 """What the co-visibility boxes cost (include/oetr_covis.h, imagematching_oetr_amd/csrc/covis.hip), in one run:
 
 For 8 and 32 pairs of 640 x 640 maps and 8 pairs of 1024 x 1024, with and without masks,
-1. the time of one ``oetr_covis_boxes`` call (its memsets, k_covis_warp, k_covis_finish),
+1. the time of one ``oetr_covis_boxes`` call (its clearing kernels, k_covis_warp, k_covis_finish),
 2. the time of a ``Tensor.copy_`` that moves the call's ALGORITHMIC bytes - depth1 and depth2 read once and, with
    masks, both masks cleared and written once; the copy reads half of that many bytes and writes the other half -
    the yardstick: the same bytes moved with no arithmetic,
