@@ -164,6 +164,13 @@ POSE_RANSAC_MAX_HYPOTHESES = 4096   # OETR_POSE_RANSAC_MAX_HYPOTHESES
 POSE_RANSAC_MAX_MODELS = 12288      # OETR_POSE_RANSAC_MAX_MODELS
 POSE_RANSAC_COUNTERS = 5            # OETR_POSE_RANSAC_COUNTERS
 
+# The nearest-neighbour matcher extension (include/oetr_nn_match.h): likewise
+NN_MATCH_ABI_VERSION = 1
+NN_MATCH_EXPORTS = ('oetr_nn_match_abi_version', 'oetr_nn_match_workspace_bytes', 'oetr_nn_match')
+NN_MATCH_COUNTERS = 4               # OETR_NN_MATCH_COUNTERS
+NN_MATCH_RATIO, NN_MATCH_DISTANCE, NN_MATCH_MUTUAL = 1, 2, 4   # OETR_NN_MATCH_RATIO / _DISTANCE / _MUTUAL
+NN_MATCH_MIN_D, NN_MATCH_MAX_D = 4, 512                        # OETR_NN_MATCH_MIN_D / _MAX_D
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -447,6 +454,18 @@ def load_library(path=None):
     if lib.oetr_pose_ransac_abi_version() != POSE_RANSAC_ABI_VERSION:
         raise RuntimeError(f'{p}: pose-ransac ABI version {lib.oetr_pose_ransac_abi_version()} != '
                            f'{POSE_RANSAC_ABI_VERSION}')
+    # include/oetr_nn_match.h
+    lib.oetr_nn_match_abi_version.restype = i
+    lib.oetr_nn_match_abi_version.argtypes = []
+    lib.oetr_nn_match_workspace_bytes.restype = sz
+    lib.oetr_nn_match_workspace_bytes.argtypes = [C.c_int64]
+    lib.oetr_nn_match.restype = i
+    # desc0, off0, n_kp0, desc1, off1, n_kp1, n_pairs, D, max_k0, max_k1, ratio_sq, distance_sq, flags, workspace,
+    # workspace_bytes, matches0, scores0, matches1, counts, stream
+    lib.oetr_nn_match.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, i, i, i, i, C.c_float, C.c_float, C.c_uint, vp,
+                                  sz] + [vp] * 5
+    if lib.oetr_nn_match_abi_version() != NN_MATCH_ABI_VERSION:
+        raise RuntimeError(f'{p}: nn-match ABI version {lib.oetr_nn_match_abi_version()} != {NN_MATCH_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
