@@ -99,15 +99,18 @@ class OverlapCropBatch:
     @property
     def valid(self):
         """Per pair: 1 - crops were made; 0 - the gate failed and the full images passed through;
-        -1 - a degenerate crop, or one the call's bounds do not cover (nothing written)."""
+        -1 - no crops, nothing written: a box outside the domain (a scaled coordinate that does not
+        truncate into [0, 2^31): negative, NaN, infinite; ``include/oetr_hip.h``), an empty crop, or one
+        the call's bounds do not cover."""
         return [int(g.valid) for g in self.geometry()]
 
     def crop(self, k, i):
         """``[1, C, out_h, out_w]`` view of pair ``k``'s image ``i`` (the reference's ``left[None]``)."""
         g = self.geometry()[k]
         if int(g.valid) < 0:
-            raise OetrError(f'overlap_crop_batch: pair {k} has a degenerate crop rectangle or one larger than the '
-                            'capacity (oetr_crop_info.valid == -1)')
+            raise OetrError(f'overlap_crop_batch: pair {k} has a box outside the domain (negative, non-finite or huge '
+                            'after scaling), a degenerate crop rectangle or one larger than the capacity '
+                            '(oetr_crop_info.valid == -1)')
         c, h, w = self._table.channels, int(g.out_h[i]), int(g.out_w[i])
         return self._out[k, i, :c * h * w].view(1, c, h, w)
 

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_crop_resize(CropLaunch p) {
   const float* src;
   float* dst;
   if (PASS == 1) {
-    x0 = min(g.box[im][0], p.w[im]); y0 = min(g.box[im][1], p.h[im]);
+    x0 = min(g.box[im][0], p.w[im]); y0 = min(g.box[im][1], p.h[im]);   // >= 0: crop_geometry's box domain
     sw = g.crop_w[im]; sh = g.crop_h[im];
     dw = g.new_w[im]; dh = g.new_h[im];
     spitch = p.w[im];

@@ -111,8 +111,7 @@ __global__ __launch_bounds__(256) void k_crop_batch_resize(CropBatchLaunch p) {
   const float* src;
   float* dst;
   if (PASS == 1) {
-    x0 = min(g.box[im][0], pr.w[im]); y0 = min(g.box[im][1], pr.h[im]);
-    if (x0 < 0 || y0 < 0) return;   // a box that starts outside the image is never dereferenced
+    x0 = min(g.box[im][0], pr.w[im]); y0 = min(g.box[im][1], pr.h[im]);   // >= 0: crop_geometry's box domain
     sw = g.crop_w[im]; sh = g.crop_h[im];
     dw = nw; dh = nh;
     spitch = pr.w[im];

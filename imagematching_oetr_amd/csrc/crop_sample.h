@@ -1,7 +1,7 @@
 // The arithmetic of the box -> crop step, shared by its two entries: oetr_overlap_crop (crop.hip,
 // one pair per call) and oetr_overlap_crop_batch (crop_batch.hip, n pairs per call).  ONE copy, so
 // that pair k of a batched call is the per-pair call bit for bit: the geometry (boxes x
-// overlap_scales, int truncation, the gate, patch_resize in double, rounding to size_divisor),
+// overlap_scales, the box domain, int truncation, the gate, patch_resize in double, rounding to size_divisor),
 // OpenCV's float bicubic weights, the source coordinate of an output pixel and the 4 x 4 tap sum.
 // The expressions and the order of the products and sums are those crop.hip has always had (references
 // to the reference's lines are in crop.hip's header comment).  What is NEW is that every rounding is
@@ -26,15 +26,32 @@ namespace oetr {
 template <class P>
 __device__ __forceinline__ void crop_geometry(const P& p, oetr_crop_info& g) {
   int bw[2], bh[2];
+  bool inside = true;
   for (int i = 0; i < 2; ++i) {
     for (int j = 0; j < 4; ++j) {
       // bbox * overlap_scales in float32 (torch tensor product), then .int() truncation
       const float v = p.box[i][j] * p.scale[i][j & 1];
       g.sbox[i][j] = v;
-      g.box[i][j] = (int)v;
+      // THE BOX DOMAIN, tested in float ahead of the cast (include/oetr_hip.h): the truncation toward zero
+      // must lie in [0, 2^31).  NaN fails both comparisons; -0.7 truncates to 0 and is inside.  Outside it
+      // the cast would be undefined and a negative origin would address memory before the plane.
+      const bool in_domain = v > -1.0f && v < 2147483648.0f;
+      inside = inside && in_domain;
+      g.box[i][j] = in_domain ? (int)v : 0;
     }
-    bw[i] = g.box[i][2] - g.box[i][0];
+    bw[i] = g.box[i][2] - g.box[i][0];   // both in [0, 2^31): cannot overflow
     bh[i] = g.box[i][3] - g.box[i][1];
+  }
+  if (!inside) {
+    // decided before the gate: valid = -1 whatever the gate would have said; every integer field and the
+    // ratios zero, sbox the scaled floats as they are.  No resize kernel reads or writes for this pair.
+    for (int i = 0; i < 2; ++i) {
+      for (int j = 0; j < 4; ++j) g.box[i][j] = 0;
+      g.crop_w[i] = g.crop_h[i] = g.new_w[i] = g.new_h[i] = g.out_w[i] = g.out_h[i] = 0;
+      g.ratio[i][0] = g.ratio[i][1] = 0.0;
+    }
+    g.valid = -1;
+    return;
   }
   int mn = min(min(bw[0], bh[0]), min(bw[1], bh[1]));
   bool valid = mn > 1;

@@ -1456,12 +1456,13 @@ class OverlapCrops:
     @property
     def valid(self):
         """True: crops were made; False: the gate failed and the full images passed through.
-        A degenerate crop / one beyond the buffers' capacity (``oetr_crop_info.valid == -1``,
-        where the reference raises from ``cv2.resize``) raises ``OetrError``."""
+        A box outside the domain (a scaled coordinate that does not truncate into [0, 2^31):
+        negative, NaN, infinite; ``include/oetr_hip.h``), a degenerate crop or one beyond the
+        buffers' capacity (``oetr_crop_info.valid == -1``; nothing was written) raises ``OetrError``."""
         v = int(self.geometry().valid)
         if v < 0:
-            raise OetrError('overlap_crop: degenerate crop rectangle or crop larger than the capacity '
-                            '(oetr_crop_info.valid == -1)')
+            raise OetrError('overlap_crop: box outside the domain (negative, non-finite or huge after scaling), '
+                            'degenerate crop rectangle or crop larger than the capacity (oetr_crop_info.valid == -1)')
         return bool(v)
 
     def crop(self, i):

@@ -37,7 +37,7 @@ size_t oetr_crop_batch_capacity(int channels, int max_h, int max_w, int size_div
 
 /*   pairs         device [n]        the table above; max_h / max_w bound every image of the call
  *   box1/box2     device [n][4]     the OETR boxes of the n pairs, OETR input frame (forward_dummy's
- *                                   outputs as they are: non-negative, clamped to the frame)
+ *                                   outputs as they are; any float is taken: the box domain, below)
  *   keep_aspect, size_divisor, gate_mode     as for oetr_overlap_crop, one setting for the call
  *   tmp           n*2*capacity floats of scratch between the two resize passes; may be NULL when
  *                 size_divisor == 1 (nothing is resized twice then)
@@ -46,14 +46,18 @@ size_t oetr_crop_batch_capacity(int channels, int max_h, int max_w, int size_div
  *   capacity_floats   floats per slot, at least oetr_crop_batch_capacity()
  *   info          device [n], written by the first launch
  *
- * info[k] is exactly what oetr_overlap_crop writes for pair k, including valid = 0 for a failed gate
- * (both images copied into their slots bit for bit) and valid = -1 for a degenerate crop (sizes zeroed,
- * nothing written).  The "fits" test behind valid = -1 is made against the pair's OWN capacity - its two
- * image sizes rounded up to size_divisor, what oetr_overlap_crop_capacity gives for it - not the slot's.
- * The host never reads the table, so what it cannot check is reported from the device: a pair with an
- * image larger than max_h x max_w, a size < 1 or a NULL image gets valid = -1 and is never dereferenced.
- * A side whose box starts left of / above the image (a negative coordinate: not a forward_dummy output)
- * is never read out of bounds: its pixels are left unwritten.
+ * info[k] is exactly what oetr_overlap_crop writes for pair k, for EVERY box: valid = 1 (crops made),
+ * valid = 0 for a failed gate (both images copied into their slots bit for bit) and valid = -1 (no crops:
+ * nothing read from the pair's images, nothing written to its tmp / out slots).  valid = -1 is the one
+ * rule of include/oetr_hip.h (THE BOX DOMAIN): a pair with a scaled coordinate that does not truncate into
+ * [0, 2^31) - negative, NaN, infinite, huge - tested in float before any conversion and before the gate
+ * (all integer fields and ratios zero, sbox the scaled floats); or, inside the domain, a crop that is
+ * empty or does not fit (new_* / out_* zeroed).  A record with valid = 1 therefore has box >= 0: no
+ * kernel forms an address from a negative origin.  The "fits" test is made against the pair's OWN
+ * capacity - its two image sizes rounded up to size_divisor, what oetr_overlap_crop_capacity gives for it
+ * - not the slot's.  The host never reads the table, so what it cannot check is reported from the device:
+ * a pair with an image larger than max_h x max_w, a size < 1 or a NULL image gets valid = -1 and is never
+ * dereferenced.
  *
  * Enqueue-only: no device-to-host copy, no synchronisation, no allocation; the caller owns every
  * buffer, and the call can be captured into a HIP graph (a replay sees the boxes and the table the

@@ -569,12 +569,32 @@ oetr_status oetr_neck_read_flags_async(oetr_neck_handle h, void *workspace,
  * memory) whenever it needs it.
  * Integer / ratio outputs are pinned to the reference (tests/golden/crop.npz); the
  * resize follows OpenCV's published float32 bicubic (a = -0.75) but is
- * parity-UNPINNED: cv2 is not installed where the fixtures were generated. */
+ * parity-UNPINNED: cv2 is not installed where the fixtures were generated.
+ *
+ * THE BOX DOMAIN (one rule for oetr_overlap_crop and oetr_overlap_crop_batch; the oracle
+ * states it in oracle/crop_oracle.py::in_domain).  The boxes live on the device and become
+ * addresses; the host cannot look at them, so the kernels decide.  For each of the eight
+ * scaled coordinates v = box[i][j] * scale[i][j & 1] (float32), BEFORE any conversion to
+ * an integer and before the gate:
+ *   outside   v is NaN or +-inf, v <= -1.0f or v >= 2147483648.0f - its truncation toward
+ *             zero is not in [0, 2^31).  The pair gets valid = -1 whatever the gate would
+ *             have said: every integer field and the ratios are zero, sbox holds the scaled
+ *             floats as they are, nothing is read from either image and nothing is written
+ *             to tmp / out.  (-0.7 truncates to 0 and is inside, as .int() has it.)
+ *   inside    the reference's arithmetic: the gate, clamping at the far edge, 0 for a
+ *             pass-through, -1 for an empty or oversize crop.  The differences x2 - x1 are
+ *             formed on values in [0, 2^31) and cannot overflow.
+ * A departure from the reference, whose image[:, y1:y2, x1:x2] wraps a negative start round
+ * from the far edge (usually an empty slice and a cv2.resize error, sometimes a sliver
+ * mapped back with the wrong origin) and whose .int() is undefined for such floats.  A
+ * caller that wants negative boxes clamped to the frame clamps them on the device first. */
 typedef struct {
-  int32_t valid;        /* 1: crops made; 0: gate failed, the full images passed through
-                           bit for bit (evaluation.py:142-170); -1: a crop is degenerate
-                           or exceeds the capacity (sizes zeroed, nothing written) - where
-                           the reference would raise from cv2.resize                 */
+  int32_t valid;        /* 1: crops made.  0: gate failed, the full images passed through
+                           bit for bit (evaluation.py:142-170).  -1: no crops, nothing
+                           written to tmp / out: the pair is outside the box domain
+                           (above), or inside it with a crop that is empty or exceeds the
+                           capacity - where the reference would raise from cv2.resize
+                           (new_* / out_* zeroed for both images)                     */
   int32_t box[2][4];    /* scaled boxes truncated to int, xyxy (utils.py:515-516)      */
   int32_t crop_w[2], crop_h[2]; /* slice sizes (Python slicing clamps at the border) */
   int32_t new_w[2], new_h[2];   /* patch_resize output (utils.py:476-493)            */
@@ -596,7 +616,9 @@ size_t oetr_overlap_crop_capacity(int channels, int h1, int w1, int h2, int w2,
  *   gate_mode     0: crops whenever every box side > 1 px; 1: 'pragueparks-val' rule
  *                 (additionally an integer size ratio > 2 between the two boxes)
  *   tmp           2 x capacity floats (device scratch between the two resize passes)
+ *   box1/box2 may hold any float: see THE BOX DOMAIN above (valid = -1 outside it)
  *   out1/out2     capacity floats each; hold [channels][out_h][out_w] densely packed
+ *                 at the start, the rest is not written
  *   info          device, written by the first launch                                */
 oetr_status oetr_overlap_crop(const float *image1, const float *image2, int channels,
                               int h1, int w1, int h2, int w2, const float *box1,

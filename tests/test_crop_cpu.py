@@ -80,6 +80,144 @@ def test_gate_and_geometry_edge_cases():
     assert geo[1]['ratio'] == (2.0, 2.0) and geo[1]['out'] == (104, 104)
 
 
+# ---- the box domain (oracle/crop_oracle.py::in_domain) ----------------------------------------------------
+# A literal table: written by hand from the rule and from patch_resize's arithmetic, not taken from the oracle.
+# Images: 48 x 56 and 41 x 47 (h x w), keep_aspect, size_divisor 1, the plain gate; the larger image gives the
+# target size (56 x 48).  Image 1's box is BOX1 with unit scales unless a row says otherwise: ints (3, 4, 40, 35),
+# slice 37 x 31, 56 / 37 < 48 / 31 so the width is kept: new = (56, int(56 / 37 * 31) = 46).
+NAN, INF = float('nan'), float('inf')
+DOMAIN_HW = ((48, 56), (41, 47))
+BOX1 = (3.0, 4.0, 40.0, 35.0)
+SIDE1 = dict(box=(3, 4, 40, 35), crop=(37, 31), new=(56, 46))
+
+
+def _row(name, box0, valid, side0=None, sc0=(1.0, 1.0), box1=BOX1, sc1=(1.0, 1.0)):
+    return dict(name=name, box0=box0, box1=box1, sc0=sc0, sc1=sc1, valid=valid, side0=side0)
+
+
+DOMAIN_TABLE = [
+    # inside: slice 45 x 34, 56 / 45 < 48 / 34 -> new = (56, int(56 / 45 * 34) = 42)
+    _row('base', (5.0, 6.0, 50.0, 40.0), 1, dict(box=(5, 6, 50, 40), crop=(45, 34), new=(56, 42))),
+    # each of the four coordinates of image 0 alone at -5, and one of image 1
+    _row('x1=-5', (-5.0, 6.0, 50.0, 40.0), -1),
+    _row('y1=-5', (5.0, -5.0, 50.0, 40.0), -1),
+    _row('x2=-5', (5.0, 6.0, -5.0, 40.0), -1),
+    _row('y2=-5', (5.0, 6.0, 50.0, -5.0), -1),
+    _row('image 1 y1=-5', (5.0, 6.0, 50.0, 40.0), -1, box1=(3.0, -5.0, 40.0, 35.0)),
+    # the lower edge of the rule: -1.0 truncates to -1 (outside), -0.999 to 0 (inside: slice 50 x 34, new_h = int(1.12 * 34) = 38)
+    _row('x1=-1.0', (-1.0, 6.0, 50.0, 40.0), -1),
+    _row('y1=-1.0', (5.0, -1.0, 50.0, 40.0), -1),
+    _row('x1=-0.999', (-0.999, 6.0, 50.0, 40.0), 1, dict(box=(0, 6, 50, 40), crop=(50, 34), new=(56, 38))),
+    # the upper edge: the largest float32 below 2^31 is inside (the stop is clamped at the far edge: slice 51 x 34,
+    # new_h = int(56 / 51 * 34) = 37); 2^31 itself and beyond are outside
+    _row('x2=2147483520', (5.0, 6.0, 2147483520.0, 40.0), 1, dict(box=(5, 6, 2147483520, 40), crop=(51, 34), new=(56, 37))),
+    _row('x2=2^31', (5.0, 6.0, 2147483648.0, 40.0), -1),
+    _row('x2=3e9', (5.0, 6.0, 3e9, 40.0), -1),
+    _row('x1=-3e9', (-3e9, 6.0, 50.0, 40.0), -1),
+    _row('y2=nan', (5.0, 6.0, 50.0, NAN), -1),
+    _row('x1=nan', (NAN, 6.0, 50.0, 40.0), -1),
+    _row('x2=+inf', (5.0, 6.0, INF, 40.0), -1),
+    _row('y1=-inf', (5.0, -INF, 50.0, 40.0), -1),
+    _row('image 1 x2=+inf', (5.0, 6.0, 50.0, 40.0), -1, box1=(3.0, 4.0, INF, 35.0)),
+    # negative only through the scale: -0.6 * 1.6 = -0.96 -> 0 (inside; 30 * 1.6 = 48 in float32: slice 48 x 34,
+    # new_h = int(56 / 48 * 34) = 39); -0.6 * 2.0 = -1.2 (outside)
+    _row('scale 1.6', (-0.6, 6.0, 30.0, 40.0), 1, dict(box=(0, 6, 48, 40), crop=(48, 34), new=(56, 39)), sc0=(1.6, 1.0)),
+    _row('scale 2.0', (-0.6, 6.0, 30.0, 40.0), -1, sc0=(2.0, 1.0)),
+    _row('scale 2.0 to -8', (-4.0, -4.0, 25.0, 20.0), -1, sc0=(2.0, 2.0)),
+    # a negative coordinate that would also have failed the gate (half a pixel wide): -1, not 0
+    _row('negative and thin', (-5.0, 6.0, -4.5, 40.0), -1),
+    # inside the domain, as before: an inverted box fails the gate (pass-through); a box wholly past the far edge
+    # passes it and leaves an empty slice (-1); a stop alone past the far edge is clamped (slice 51 x 34)
+    _row('inverted', (50.0, 6.0, 5.0, 40.0), 0),
+    _row('past the far edge', (60.0, 6.0, 90.0, 40.0), -1, dict(box=(60, 6, 90, 40), crop=(0, 34), new=(0, 0))),
+    _row('stop past the far edge', (5.0, 6.0, 70.0, 40.0), 1, dict(box=(5, 6, 70, 40), crop=(51, 34), new=(56, 37))),
+]
+
+
+def domain_row_boxes(row):
+    return torch.tensor(row['box0'], dtype=torch.float32), torch.tensor(row['box1'], dtype=torch.float32)
+
+
+def test_box_domain_table():
+    names = [r['name'] for r in DOMAIN_TABLE]
+    assert len(set(names)) == len(names)
+    im0, im1 = torch.rand(1, 1, *DOMAIN_HW[0]), torch.rand(1, 1, *DOMAIN_HW[1])
+    for row in DOMAIN_TABLE:
+        b0, b1 = domain_row_boxes(row)
+        rec = cro.crop_record(*DOMAIN_HW, b0, b1, row['sc0'], row['sc1'], True, 1, False)
+        assert rec['valid'] == row['valid'], (row['name'], rec)
+        out = cro.overlap_crop(im0, im1, b0, b1, row['sc0'], row['sc1'], True, 1, False)
+        assert out['valid'] == row['valid'] and type(out['valid']) is (int if row['valid'] < 0 else bool), row['name']
+        if row['valid'] < 0:
+            assert out['crop0'] is None and out['crop1'] is None, row['name']
+            assert rec['new_w'] == rec['new_h'] == rec['out_w'] == rec['out_h'] == [0, 0], row['name']
+        if row['valid'] == 0:
+            assert rec['box'] == [[0, 0, 56, 48], [0, 0, 47, 41]] and rec['crop_w'] == rec['out_w'] == [56, 47], row['name']
+            assert rec['crop_h'] == rec['out_h'] == [48, 41] and rec['ratio'] == [[1.0, 1.0]] * 2, row['name']
+            assert out['crop0'] is im0 and out['crop1'] is im1
+        if row['side0'] is not None:         # the integer fields of a record inside the domain
+            new1 = SIDE1['new'] if row['valid'] == 1 else (0, 0)       # one empty side zeroes the sizes of both
+            for i, want in ((0, row['side0']), (1, dict(SIDE1, new=new1))):
+                got = dict(box=tuple(rec['box'][i]), crop=(rec['crop_w'][i], rec['crop_h'][i]), new=(rec['new_w'][i], rec['new_h'][i]))
+                assert got == want, (row['name'], i, got)
+                assert (rec['out_w'][i], rec['out_h'][i]) == want['new'], (row['name'], i)
+        if row['valid'] == 1:
+            assert tuple(out['crop0'].shape) == (1, 1, rec['out_h'][0], rec['out_w'][0]), row['name']
+        if row['valid'] == -1 and row['side0'] is None:      # outside the domain: all integers and ratios zero, sbox as scaled
+            assert rec['box'] == [[0] * 4] * 2 and rec['crop_w'] == rec['crop_h'] == [0, 0] and rec['ratio'] == [[0.0, 0.0]] * 2
+            sb = cro.scale_boxes(b0, b1, row['sc0'], row['sc1'])
+            assert np.array_equal(np.float32(rec['sbox']), torch.stack(sb).numpy(), equal_nan=True), row['name']
+    assert {r['valid'] for r in DOMAIN_TABLE} == {1, 0, -1}
+
+
+def test_in_domain_slice_and_size_come_from_one_rectangle():
+    """Independent of the oracle's own clamping: for random NON-NEGATIVE integer boxes - starts and stops past
+    the far edge, inverted and empty ones included - the size the oracle reports is the shape of Python's
+    ``img[0, :, y1:y2, x1:x2]`` and the patch it resizes is that slice."""
+    rng = np.random.default_rng(21)
+    img = torch.rand(1, 2, 23, 31, generator=torch.Generator().manual_seed(21))
+    other = (19, 40)
+    n_past = n_empty = 0
+    for _ in range(400):
+        x1, x2 = (int(v) for v in rng.integers(0, 45, size=2))
+        y1, y2 = (int(v) for v in rng.integers(0, 35, size=2))
+        sb = torch.tensor([x1, y1, x2, y2], dtype=torch.float32)
+        g = cro.crop_geometry(tuple(img.shape[2:]), other, sb, torch.tensor([1.0, 2.0, 30.0, 15.0]), True, 1)[0]
+        want = img[0, :, y1:y2, x1:x2]
+        assert g['box'] == (x1, y1, x2, y2)
+        assert g['crop'] == (want.shape[2], want.shape[1]), (x1, y1, x2, y2, g)
+        patch = cro.crop_patch(img, g['rect'])
+        assert patch.shape == (want.shape[1], want.shape[2], 2)
+        assert np.array_equal(patch, want.permute(1, 2, 0).numpy() * 255)
+        n_past += x1 > 31 or y1 > 23 or x2 > 31 or y2 > 23
+        n_empty += want.numel() == 0
+    assert n_past > 100 and 50 < n_empty < 350
+
+
+def test_fuzz_cases_are_unchanged_by_the_domain_rule():
+    """``tests/crop_fuzz_expected.json`` holds what ``overlap_crop`` of the oracle gave for the 60 fuzz cases
+    (``tests/test_gpu_crop_batch.py::fuzz_cases``) BEFORE the box domain was stated: gate, scaled boxes, ratios,
+    shapes and pixel checksums.  (The oracle's own record, not the reference's output: it lies beside the other
+    expected-result files, not among the regenerated fixtures of ``tests/golden/``.)  Every case lies inside the
+    domain, and the oracle still gives exactly that."""
+    import json
+    from pathlib import Path
+    from tests.test_gpu_crop_batch import fuzz_cases, image
+    want = json.loads((Path(__file__).resolve().parent / 'crop_fuzz_expected.json').read_text())['cases']
+    cases = fuzz_cases()
+    assert len(want) == len(cases) == 60
+    for ci, (c, w) in enumerate(zip(cases, want)):
+        keep, div, pp = c['mode']
+        assert cro.in_domain(*cro.scale_boxes(c['b0'], c['b1'], c['sc0'], c['sc1'])), ci
+        ref = cro.overlap_crop(image(c['hw0']), image(c['hw1']), c['b0'], c['b1'], c['sc0'], c['sc1'], keep, div, pp)
+        assert ref['valid'] is bool(w['valid']), ci
+        for i, s in enumerate('01'):
+            assert [float(v) for v in ref['bbox' + s].reshape(-1)] == w['bbox'][i], (ci, i)
+            assert [float(v) for v in ref['ratio' + s]] == w['ratio'][i], (ci, i)
+            assert list(ref['crop' + s].shape) == w['shape'][i] and orc.checksum(ref['crop' + s]) == w['checksum'][i], (ci, i)
+    assert 0 < sum(w['valid'] for w in want) < 60
+
+
 def test_bicubic_agrees_with_an_independent_implementation():
     """cv2 is not installed, so OpenCV's own output cannot pin :func:`bicubic_resize`; what
     can be checked is that the restatement agrees with an INDEPENDENT implementation of the
