@@ -23,14 +23,15 @@ from .bank import FeatureBank  # noqa: F401
 from .covis import overlap_boxes_from_batch, overlap_boxes_from_depth  # noqa: F401
 from .covis_set import DepthSet, mine_pairs, overlap_boxes_indexed  # noqa: F401
 from .crop_batch import OverlapCropBatch, crop_pair_table, keypoints_to_origin, overlap_crop_batch  # noqa: F401
-from .evaluate import (evaluate_dummy, evaluate_indexed, keypoint_repeatability, match_pose_auc, match_precision,  # noqa: F401
-                       pose_auc, pose_errors)
+from .evaluate import (evaluate_dummy, evaluate_indexed, homography_auc, homography_errors, keypoint_repeatability,  # noqa: F401
+                       match_homography_auc, match_pose_auc, match_precision, pose_auc, pose_errors)
 from .match_score import match_params, score_matches  # noqa: F401
 from .keypoint_score import ground_truth_matches, score_keypoints  # noqa: F401
 from .match_assembly import assemble_matches, few_match_pairs  # noqa: F401
 from .homography import (homography_accuracy, homography_params, overlap_boxes_from_homography,  # noqa: F401
                          rescale_homography, score_matches_homography)
 from .pose_ransac import estimate_poses  # noqa: F401
+from .homography_ransac import estimate_homographies, transfer_points  # noqa: F401
 from .nn_match import match_counts, match_descriptors  # noqa: F401
 from .reader import overlap_frame, read_overlap_images  # noqa: F401
 from .hip_engine import (FLAG_EXCHANGE, FLAG_F16_RANGE, FLAG_INDEX, FLAG_INVALID, FULL_ATTENTION_VARIANTS, HotPathEngine, KernelTrace, NeckEngine, OetrError,  # noqa: F401
@@ -51,4 +52,5 @@ __all__ = ['Cfg', 'get_cfg_defaults', 'OETR', 'build_detectors',
            'homography_params', 'rescale_homography', 'score_matches_homography', 'homography_accuracy',
            'overlap_boxes_from_homography',
            'estimate_poses', 'pose_errors', 'pose_auc', 'match_pose_auc',
-           'match_descriptors', 'match_counts']
+           'match_descriptors', 'match_counts',
+           'estimate_homographies', 'transfer_points', 'homography_errors', 'homography_auc', 'match_homography_auc']

@@ -263,3 +263,36 @@ def match_pose_auc(result, thresholds=(5, 10, 20)):
     errs = pose_errors(result)
     return {'auc': [100.0 * a for a in pose_auc(errs['pose_error'], thresholds)], 'thresholds': tuple(thresholds),
             'n_pairs': int(errs['pose_error'].size), 'n_no_pose': int(np.isinf(errs['pose_error']).sum()), **errs}
+
+
+def homography_errors(result):
+    """The mean corner error per pair of a ``homography_ransac.estimate_homographies`` result, from ONE device
+    read of its ``corner_sq`` and ``counts``: the square roots of the four squared corner distances - left to
+    the host, the project's standing departure - added in corner order, over 4, in pixels of picture 2.  A pair
+    without a homography (selected model -1), without ground truth, or with a corner on the horizon line (a
+    distance that is not finite) gives ``inf``.  -> float64 ``[P]``."""
+    sq, counts = result['corner_sq'], result['counts']
+    if torch.is_tensor(sq):
+        # both in ONE float64 tensor (exact for these integers): one read
+        packed = torch.cat([sq.reshape(-1, 4), counts.reshape(-1, 6).to(torch.float64)], 1).cpu().numpy()
+        sq, counts = packed[:, :4], packed[:, 4:]
+    sq, counts = np.asarray(sq, np.float64).reshape(-1, 4), np.asarray(counts).reshape(-1, 6)
+    none = ~np.isfinite(sq).all(1) | (counts[:, 2] < 0)
+    with np.errstate(all='ignore'):
+        d = np.sqrt(np.where(none[:, None], 0.0, sq))
+        mean = (((d[:, 0] + d[:, 1]) + d[:, 2]) + d[:, 3]) / 4.0
+    return np.where(none, np.inf, mean)
+
+
+def homography_auc(errors, thresholds=(3, 5, 10)):
+    """:func:`pose_auc` of mean corner errors in pixels: the area under the recall curve up to each threshold,
+    over the threshold.  ``errors``: an array as :func:`homography_errors` returns it."""
+    return pose_auc(np.asarray(errors, np.float64), thresholds)
+
+
+def match_homography_auc(result, thresholds=(3, 5, 10)):
+    """:func:`homography_errors` and :func:`homography_auc` together, times 100:
+    ``{'auc': [AUC@3, AUC@5, AUC@10], 'thresholds', 'corner_error', 'n_pairs', 'n_no_homography'}``."""
+    errs = homography_errors(result)
+    return {'auc': [100.0 * a for a in homography_auc(errs, thresholds)], 'thresholds': tuple(thresholds),
+            'corner_error': errs, 'n_pairs': int(errs.size), 'n_no_homography': int(np.isinf(errs).sum())}

@@ -171,6 +171,15 @@ NN_MATCH_COUNTERS = 4               # OETR_NN_MATCH_COUNTERS
 NN_MATCH_RATIO, NN_MATCH_DISTANCE, NN_MATCH_MUTUAL = 1, 2, 4   # OETR_NN_MATCH_RATIO / _DISTANCE / _MUTUAL
 NN_MATCH_MIN_D, NN_MATCH_MAX_D = 4, 512                        # OETR_NN_MATCH_MIN_D / _MAX_D
 
+# The homography-estimation extension (include/oetr_homography_ransac.h): likewise
+HOMOGRAPHY_RANSAC_ABI_VERSION = 1
+HOMOGRAPHY_RANSAC_EXPORTS = ('oetr_homography_ransac_abi_version', 'oetr_homography_ransac_workspace_bytes',
+                             'oetr_homography_ransac')
+HOMOGRAPHY_RANSAC_MAX_HYPOTHESES = 4096   # OETR_HOMOGRAPHY_RANSAC_MAX_HYPOTHESES
+HOMOGRAPHY_RANSAC_MAX_MODELS = 4096       # OETR_HOMOGRAPHY_RANSAC_MAX_MODELS
+HOMOGRAPHY_RANSAC_MAX_REFIT = 4           # OETR_HOMOGRAPHY_RANSAC_MAX_REFIT
+HOMOGRAPHY_RANSAC_COUNTERS = 6            # OETR_HOMOGRAPHY_RANSAC_COUNTERS
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -466,6 +475,19 @@ def load_library(path=None):
                                   sz] + [vp] * 5
     if lib.oetr_nn_match_abi_version() != NN_MATCH_ABI_VERSION:
         raise RuntimeError(f'{p}: nn-match ABI version {lib.oetr_nn_match_abi_version()} != {NN_MATCH_ABI_VERSION}')
+    # include/oetr_homography_ransac.h
+    lib.oetr_homography_ransac_abi_version.restype = i
+    lib.oetr_homography_ransac_abi_version.argtypes = []
+    lib.oetr_homography_ransac_workspace_bytes.restype = sz
+    lib.oetr_homography_ransac_workspace_bytes.argtypes = [i, i]
+    lib.oetr_homography_ransac.restype = i
+    # params, offsets, pair_ids, n_pairs, k1, k2, n_matches, n_hyp, seed, px_thr, refit_iters, models_in, n_models_in,
+    # workspace, workspace_bytes, model, H, corner_sq, counts, inliers, stream
+    lib.oetr_homography_ransac.argtypes = [vp, vp, vp, i, vp, vp, C.c_int64, i, C.c_uint32, C.c_double, i, vp, i, vp,
+                                           sz] + [vp] * 6
+    if lib.oetr_homography_ransac_abi_version() != HOMOGRAPHY_RANSAC_ABI_VERSION:
+        raise RuntimeError(f'{p}: homography-ransac ABI version {lib.oetr_homography_ransac_abi_version()} != '
+                           f'{HOMOGRAPHY_RANSAC_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
