@@ -31,6 +31,7 @@ from .match_assembly import assemble_matches, few_match_pairs  # noqa: F401
 from .homography import (homography_accuracy, homography_params, overlap_boxes_from_homography,  # noqa: F401
                          rescale_homography, score_matches_homography)
 from .pose_ransac import estimate_poses  # noqa: F401
+from .pose_refit import refine_poses  # noqa: F401
 from .homography_ransac import estimate_homographies, transfer_points  # noqa: F401
 from .nn_match import match_counts, match_descriptors  # noqa: F401
 from .reader import overlap_frame, read_overlap_images  # noqa: F401
@@ -51,6 +52,6 @@ __all__ = ['Cfg', 'get_cfg_defaults', 'OETR', 'build_detectors',
            'assemble_matches', 'few_match_pairs',
            'homography_params', 'rescale_homography', 'score_matches_homography', 'homography_accuracy',
            'overlap_boxes_from_homography',
-           'estimate_poses', 'pose_errors', 'pose_auc', 'match_pose_auc',
+           'estimate_poses', 'refine_poses', 'pose_errors', 'pose_auc', 'match_pose_auc',
            'match_descriptors', 'match_counts',
            'estimate_homographies', 'transfer_points', 'homography_errors', 'homography_auc', 'match_homography_auc']

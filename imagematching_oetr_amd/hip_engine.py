@@ -180,6 +180,12 @@ HOMOGRAPHY_RANSAC_MAX_MODELS = 4096       # OETR_HOMOGRAPHY_RANSAC_MAX_MODELS
 HOMOGRAPHY_RANSAC_MAX_REFIT = 4           # OETR_HOMOGRAPHY_RANSAC_MAX_REFIT
 HOMOGRAPHY_RANSAC_COUNTERS = 6            # OETR_HOMOGRAPHY_RANSAC_COUNTERS
 
+# The pose-refit extension (include/oetr_pose_refit.h): likewise
+POSE_REFIT_ABI_VERSION = 1
+POSE_REFIT_EXPORTS = ('oetr_pose_refit_abi_version', 'oetr_pose_refit')
+POSE_REFIT_MAX_ITERS = 8            # OETR_POSE_REFIT_MAX_ITERS
+POSE_REFIT_COUNTERS = 5             # OETR_POSE_REFIT_COUNTERS
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -488,6 +494,16 @@ def load_library(path=None):
     if lib.oetr_homography_ransac_abi_version() != HOMOGRAPHY_RANSAC_ABI_VERSION:
         raise RuntimeError(f'{p}: homography-ransac ABI version {lib.oetr_homography_ransac_abi_version()} != '
                            f'{HOMOGRAPHY_RANSAC_ABI_VERSION}')
+    # include/oetr_pose_refit.h
+    lib.oetr_pose_refit_abi_version.restype = i
+    lib.oetr_pose_refit_abi_version.argtypes = []
+    lib.oetr_pose_refit.restype = i
+    # params, offsets, n_pairs, k1, k2, n_matches, model_in, px_thr, refit_iters, model, pose, cosines, counts, inliers,
+    # stream
+    lib.oetr_pose_refit.argtypes = [vp, vp, i, vp, vp, C.c_int64, vp, C.c_double, i] + [vp] * 6
+    if lib.oetr_pose_refit_abi_version() != POSE_REFIT_ABI_VERSION:
+        raise RuntimeError(f'{p}: pose-refit ABI version {lib.oetr_pose_refit_abi_version()} != '
+                           f'{POSE_REFIT_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
