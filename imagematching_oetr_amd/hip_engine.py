@@ -66,6 +66,13 @@ class _CropPair(C.Structure):
                 ('scale', (C.c_float * 2) * 2)]
 
 
+class _KeypointMap(C.Structure):
+    """``oetr_keypoint_map`` (include/oetr_keypoint_select.h): one row of a keypoint-selection call's map table."""
+    _fields_ = [('scores', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('score_stride', C.c_int64),
+                ('desc', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('desc_stride', C.c_int64 * 3),
+                ('pixel_offset', C.c_int64)]
+
+
 class _CovisMap(C.Structure):
     """``oetr_covis_map`` (include/oetr_covis_set.h): one row of a depth-map set's device table."""
     _fields_ = [('depth', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32)]
@@ -185,6 +192,17 @@ POSE_REFIT_ABI_VERSION = 1
 POSE_REFIT_EXPORTS = ('oetr_pose_refit_abi_version', 'oetr_pose_refit')
 POSE_REFIT_MAX_ITERS = 8            # OETR_POSE_REFIT_MAX_ITERS
 POSE_REFIT_COUNTERS = 5             # OETR_POSE_REFIT_COUNTERS
+
+# The keypoint-selection extension (include/oetr_keypoint_select.h): likewise
+KEYPOINT_SELECT_ABI_VERSION = 1
+KEYPOINT_SELECT_EXPORTS = ('oetr_keypoint_select_abi_version', 'oetr_keypoint_select_workspace_bytes',
+                           'oetr_keypoint_select')
+KEYPOINT_SELECT_COUNTERS = 2        # OETR_KEYPOINT_SELECT_COUNTERS
+KEYPOINT_SELECT_MAX_RADIUS = 8      # OETR_KEYPOINT_SELECT_MAX_RADIUS
+KEYPOINT_SELECT_MAX_KEYPOINTS = 4096   # OETR_KEYPOINT_SELECT_MAX_KEYPOINTS
+KEYPOINT_SELECT_MIN_D, KEYPOINT_SELECT_MAX_D = 4, 512   # OETR_KEYPOINT_SELECT_MIN_D / _MAX_D
+KEYPOINT_SELECT_MAX_SIDE = 8192     # OETR_KEYPOINT_SELECT_MAX_SIDE
+KEYPOINT_SELECT_PIXEL_ALIGN = 64    # OETR_KEYPOINT_SELECT_PIXEL_ALIGN
 
 
 def hot_path_keys():
@@ -504,6 +522,18 @@ def load_library(path=None):
     if lib.oetr_pose_refit_abi_version() != POSE_REFIT_ABI_VERSION:
         raise RuntimeError(f'{p}: pose-refit ABI version {lib.oetr_pose_refit_abi_version()} != '
                            f'{POSE_REFIT_ABI_VERSION}')
+    # include/oetr_keypoint_select.h
+    lib.oetr_keypoint_select_abi_version.restype = i
+    lib.oetr_keypoint_select_abi_version.argtypes = []
+    lib.oetr_keypoint_select_workspace_bytes.restype = sz
+    lib.oetr_keypoint_select_workspace_bytes.argtypes = [C.c_int64, i, i]
+    lib.oetr_keypoint_select.restype = i
+    # maps, n_maps, max_pixels, total_pixels, D, nms_radius, threshold, remove_borders, max_keypoints, cell, workspace,
+    # workspace_bytes, keypoints, scores, descriptors, offsets, counts, stream
+    lib.oetr_keypoint_select.argtypes = [vp, i, C.c_int64, C.c_int64, i, i, C.c_float, i, i, i, vp, sz] + [vp] * 6
+    if lib.oetr_keypoint_select_abi_version() != KEYPOINT_SELECT_ABI_VERSION:
+        raise RuntimeError(f'{p}: keypoint-select ABI version {lib.oetr_keypoint_select_abi_version()} != '
+                           f'{KEYPOINT_SELECT_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
