@@ -34,6 +34,7 @@ from .pose_ransac import estimate_poses  # noqa: F401
 from .pose_refit import refine_poses  # noqa: F401
 from .homography_ransac import estimate_homographies, transfer_points  # noqa: F401
 from .nn_match import match_counts, match_descriptors  # noqa: F401
+from .dense_match import dense_match_counts, match_dense  # noqa: F401
 from .keypoint_select import keypoint_counts, keypoint_map_table, select_keypoints  # noqa: F401
 from .reader import overlap_frame, read_overlap_images  # noqa: F401
 from .hip_engine import (FLAG_EXCHANGE, FLAG_F16_RANGE, FLAG_INDEX, FLAG_INVALID, FULL_ATTENTION_VARIANTS, HotPathEngine, KernelTrace, NeckEngine, OetrError,  # noqa: F401
@@ -56,4 +57,5 @@ __all__ = ['Cfg', 'get_cfg_defaults', 'OETR', 'build_detectors',
            'estimate_poses', 'refine_poses', 'pose_errors', 'pose_auc', 'match_pose_auc',
            'match_descriptors', 'match_counts',
            'keypoint_map_table', 'select_keypoints', 'keypoint_counts',
+           'match_dense', 'dense_match_counts',
            'estimate_homographies', 'transfer_points', 'homography_errors', 'homography_auc', 'match_homography_auc']

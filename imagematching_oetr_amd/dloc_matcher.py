@@ -13,6 +13,7 @@ the lowest index, and ``M = 1`` with a ratio threshold passes the ratio test whe
 import torch
 
 from .dloc_overlap import _BaseModel
+from .dense_match import match_dense
 from .nn_match import match_descriptors
 
 
@@ -48,3 +49,54 @@ class NearestNeighborPluginMixin:
 
 class NearestNeighbor(NearestNeighborPluginMixin, _BaseModel):
     """The stand-alone form: nothing of the reference needs to be importable."""
+
+
+class DualSoftmaxPluginMixin:
+    """A detector-free matcher in the shape of the reference's ``direct`` plug-ins (``dloc/core/matchers/loftr.py``):
+    ``required_inputs`` are the two images, ``net(image0, image1)`` - a torch module or callable given at construction
+    - returns the two coarse feature maps ``[B,D,h0,w0]`` and ``[B,D,h1,w1]`` (float32), and the matching head is
+    :func:`imagematching_oetr_amd.match_dense`: one device call for the whole batch.  The result has one entry per
+    batch element, as the reference's lists have: ``keypoints0`` ``[L,2]``, ``keypoints1`` ``[S,2]`` (every token's
+    pixel position in its image), ``matches0`` int64 ``[L]`` with ``-1`` left in place (the reference's ``process()``
+    handles those through ``matches > -1``) and ``matching_scores0`` ``[L]``."""
+
+    default_conf = {
+        'temperature': 0.1,
+        'threshold': 0.2,
+        'border_rm': 2,
+        'cell': 8,
+    }
+    required_inputs = ['image0', 'image1']
+    required_data_keys = ['image0', 'image1']
+
+    def _init(self, conf, model_path):
+        pass
+
+    def _forward(self, data):
+        if self.net is None:
+            raise ValueError('DualSoftmax needs `net`: a callable (image0, image1) -> the two coarse feature maps')
+        f0, f1 = self.net(data['image0'], data['image1'])
+        if f0.dim() != 4 or f1.dim() != 4 or f0.shape[:2] != f1.shape[:2]:
+            raise ValueError(f'net returned {tuple(f0.shape)} and {tuple(f1.shape)}: need [B,D,h0,w0] and [B,D,h1,w1]')
+        B, D, h0, w0 = (int(v) for v in f0.shape)
+        h1, w1 = int(f1.shape[2]), int(f1.shape[3])
+        L, S = h0 * w0, h1 * w1
+        dev = f0.device
+        steps = torch.arange(B + 1, dtype=torch.int32, device=dev)
+        grids = torch.tensor([[h0, w0], [h1, w1]], dtype=torch.int32, device=dev)
+        res = match_dense(f0.permute(0, 2, 3, 1).reshape(B * L, D), f1.permute(0, 2, 3, 1).reshape(B * S, D),
+                          offsets0=steps * L, offsets1=steps * S, grids0=grids[0].expand(B, 2).contiguous(),
+                          grids1=grids[1].expand(B, 2).contiguous(), max_k0=L, max_k1=S,
+                          temperature=self.conf['temperature'], threshold=self.conf['threshold'],
+                          border_rm=self.conf['border_rm'], cell=self.conf['cell'])
+        return {'keypoints0': list(res['keypoints0'].view(B, L, 2)), 'keypoints1': list(res['keypoints1'].view(B, S, 2)),
+                'matches0': list(res['matches0'].view(B, L).long()),
+                'matching_scores0': list(res['matching_scores0'].view(B, L))}
+
+
+class DualSoftmax(DualSoftmaxPluginMixin, _BaseModel):
+    """The stand-alone form: ``DualSoftmax(conf, net=net)``; nothing of the reference needs to be importable."""
+
+    def __init__(self, conf, model_path=None, net=None):
+        super().__init__(conf, model_path)
+        self.net = net

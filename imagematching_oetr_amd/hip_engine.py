@@ -204,6 +204,14 @@ KEYPOINT_SELECT_MIN_D, KEYPOINT_SELECT_MAX_D = 4, 512   # OETR_KEYPOINT_SELECT_M
 KEYPOINT_SELECT_MAX_SIDE = 8192     # OETR_KEYPOINT_SELECT_MAX_SIDE
 KEYPOINT_SELECT_PIXEL_ALIGN = 64    # OETR_KEYPOINT_SELECT_PIXEL_ALIGN
 
+# The dual-softmax matcher extension (include/oetr_dual_softmax.h): likewise
+DUAL_SOFTMAX_ABI_VERSION = 1
+DUAL_SOFTMAX_EXPORTS = ('oetr_dual_softmax_abi_version', 'oetr_dual_softmax_workspace_bytes',
+                        'oetr_dual_softmax_match')
+DUAL_SOFTMAX_COUNTERS = 4           # OETR_DUAL_SOFTMAX_COUNTERS
+DUAL_SOFTMAX_PARTIALS = 8           # OETR_DUAL_SOFTMAX_PARTIALS
+DUAL_SOFTMAX_MIN_D, DUAL_SOFTMAX_MAX_D = 4, 512   # OETR_DUAL_SOFTMAX_MIN_D / _MAX_D
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -534,6 +542,19 @@ def load_library(path=None):
     if lib.oetr_keypoint_select_abi_version() != KEYPOINT_SELECT_ABI_VERSION:
         raise RuntimeError(f'{p}: keypoint-select ABI version {lib.oetr_keypoint_select_abi_version()} != '
                            f'{KEYPOINT_SELECT_ABI_VERSION}')
+    # include/oetr_dual_softmax.h
+    lib.oetr_dual_softmax_abi_version.restype = i
+    lib.oetr_dual_softmax_abi_version.argtypes = []
+    lib.oetr_dual_softmax_workspace_bytes.restype = sz
+    lib.oetr_dual_softmax_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.oetr_dual_softmax_match.restype = i
+    # feat0, off0, grids0, n_tok0, feat1, off1, grids1, n_tok1, n_pairs, D, max_k0, max_k1, scale, threshold, border_rm,
+    # cell, workspace, workspace_bytes, matches0, scores0, matches1, keypoints0, keypoints1, counts, stream
+    lib.oetr_dual_softmax_match.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, i, i, i, i, C.c_float,
+                                            C.c_float, i, i, vp, sz] + [vp] * 7
+    if lib.oetr_dual_softmax_abi_version() != DUAL_SOFTMAX_ABI_VERSION:
+        raise RuntimeError(f'{p}: dual-softmax ABI version {lib.oetr_dual_softmax_abi_version()} != '
+                           f'{DUAL_SOFTMAX_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
