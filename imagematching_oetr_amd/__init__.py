@@ -35,6 +35,7 @@ from .pose_refit import refine_poses  # noqa: F401
 from .homography_ransac import estimate_homographies, transfer_points  # noqa: F401
 from .nn_match import match_counts, match_descriptors  # noqa: F401
 from .dense_match import dense_match_counts, match_dense  # noqa: F401
+from .fine_match import fine_match_counts, fine_windows, refine_matches  # noqa: F401
 from .keypoint_select import keypoint_counts, keypoint_map_table, select_keypoints  # noqa: F401
 from .reader import overlap_frame, read_overlap_images  # noqa: F401
 from .hip_engine import (FLAG_EXCHANGE, FLAG_F16_RANGE, FLAG_INDEX, FLAG_INVALID, FULL_ATTENTION_VARIANTS, HotPathEngine, KernelTrace, NeckEngine, OetrError,  # noqa: F401
@@ -58,4 +59,5 @@ __all__ = ['Cfg', 'get_cfg_defaults', 'OETR', 'build_detectors',
            'match_descriptors', 'match_counts',
            'keypoint_map_table', 'select_keypoints', 'keypoint_counts',
            'match_dense', 'dense_match_counts',
+           'fine_windows', 'refine_matches', 'fine_match_counts',
            'estimate_homographies', 'transfer_points', 'homography_errors', 'homography_auc', 'match_homography_auc']

@@ -212,6 +212,17 @@ DUAL_SOFTMAX_COUNTERS = 4           # OETR_DUAL_SOFTMAX_COUNTERS
 DUAL_SOFTMAX_PARTIALS = 8           # OETR_DUAL_SOFTMAX_PARTIALS
 DUAL_SOFTMAX_MIN_D, DUAL_SOFTMAX_MAX_D = 4, 512   # OETR_DUAL_SOFTMAX_MIN_D / _MAX_D
 
+# The fine-match extension (include/oetr_fine_match.h): likewise
+FINE_MATCH_ABI_VERSION = 1
+FINE_MATCH_EXPORTS = ('oetr_fine_match_abi_version', 'oetr_fine_match_workspace_bytes', 'oetr_fine_windows',
+                      'oetr_fine_refine')
+FINE_MATCH_WINDOW_COUNTERS = 2      # OETR_FINE_MATCH_WINDOW_COUNTERS
+FINE_MATCH_COUNTERS = 3             # OETR_FINE_MATCH_COUNTERS
+FINE_MATCH_PARTIALS = 16            # OETR_FINE_MATCH_PARTIALS
+FINE_MATCH_MIN_C, FINE_MATCH_MAX_C = 4, 512   # OETR_FINE_MATCH_MIN_C / _MAX_C
+FINE_MATCH_MAX_STRIDE = 8           # OETR_FINE_MATCH_MAX_STRIDE
+FINE_MATCH_WINDOWS = (3, 5, 7)
+
 
 def hot_path_keys():
     """State-dict keys (reference checkpoint names) the library consumes."""
@@ -555,6 +566,24 @@ def load_library(path=None):
     if lib.oetr_dual_softmax_abi_version() != DUAL_SOFTMAX_ABI_VERSION:
         raise RuntimeError(f'{p}: dual-softmax ABI version {lib.oetr_dual_softmax_abi_version()} != '
                            f'{DUAL_SOFTMAX_ABI_VERSION}')
+    # include/oetr_fine_match.h
+    lib.oetr_fine_match_abi_version.restype = i
+    lib.oetr_fine_match_abi_version.argtypes = []
+    lib.oetr_fine_match_workspace_bytes.restype = sz
+    lib.oetr_fine_match_workspace_bytes.argtypes = [i]
+    lib.oetr_fine_windows.restype = i
+    # matches0, off0, off1, grids0, grids1, n_tok0, n_tok1, n_pairs, max_k0, fine0, foff0, fgrids0, n_fine0, fine1, foff1,
+    # fgrids1, n_fine1, C, W, stride, max_matches, workspace, workspace_bytes, rows, moffsets, counts, win0, win1, stream
+    lib.oetr_fine_windows.argtypes = ([vp] * 5 + [C.c_int64, C.c_int64, i, i, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64,
+                                                 i, i, i, C.c_int64, vp, sz] + [vp] * 6)
+    lib.oetr_fine_refine.restype = i
+    # win0, win1, rows, moffsets, wcounts, n_pairs, max_matches, keypoints0, off0, n_tok0, keypoints1, off1, n_tok1, C, W,
+    # fine_cell, expec, mkpts0, mkpts1, keypoints1_f, counts, stream
+    lib.oetr_fine_refine.argtypes = ([vp] * 5 + [i, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, i, i, C.c_float]
+                                     + [vp] * 6)
+    if lib.oetr_fine_match_abi_version() != FINE_MATCH_ABI_VERSION:
+        raise RuntimeError(f'{p}: fine-match ABI version {lib.oetr_fine_match_abi_version()} != '
+                           f'{FINE_MATCH_ABI_VERSION}')
     if path is None:
         _lib = lib
     return lib
